@@ -5,6 +5,8 @@ on synthetic CelebA-shaped 128x128 batches, one process per GPU.
     python bench.py --gpus N --steps K --warmup W
     (N > 1: either under a launcher -- python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ... --
      or bare: the script then starts its N ranks itself as a child torch.distributed.run)
+    --dump-outputs DIR additionally writes what the last timed step computed (a fixed sample of G's, D's and Gs's variables) as
+    DIR/<name>.npy: the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 
 A "step" is one iteration of the reference's host loop (training/training_loop.py:466-482): G step,
 G path-length reg every 4th, D step + Gs EMA, D R1 reg every 16th; it advances the image counter by
@@ -124,7 +126,29 @@ def parse_args():
     p.add_argument('--revalidate-every', type=int, default=0, help='stress check: every N iterations (untimed work inside the loop) replay each captured op against its eager execution again; the results land in hip_graphs.checks')
     p.add_argument('--op-times', action='store_true', help='also report the mean device time of each training op (HIP events)')
     p.add_argument('--conv-shapes', default=None, metavar='FILE', help='write the per-shape table of the conv family inside the replayed graphs (device stamps) to FILE')
+    p.add_argument('--dump-outputs', default=None, metavar='DIR', help='after the timed steps, write what the last timed iteration computed -- the variables of '
+                   'G, D and Gs, a fixed sample of %d values per network -- as DIR/<G|D|Gs>.npy (float32); e.g. bench_outputs/' % DUMP_PER_NETWORK)
     return p.parse_args()
+
+
+DUMP_PER_NETWORK = 1 << 22      # --dump-outputs: 3 networks x 16 MiB of float32
+DUMP_SAMPLE_SEED = 20261015
+
+
+def dump_outputs(directory, nets):
+    """--dump-outputs: what a caller of the timed loop receives -- the networks' variables (all of them, in the network's own order,
+    flattened) as they stand after the last timed iteration.  The bench networks hold ~24 M values each, so a larger network is
+    written as a fixed sample of DUMP_PER_NETWORK values: positions drawn from their own seeded stream (the same in every run and
+    every build; the loop's global NumPy stream is not touched), in ascending order."""
+    import numpy as np
+    import torch
+    os.makedirs(directory, exist_ok=True)
+    for name, net in nets.items():
+        flat = torch.cat([v.detach().reshape(-1).float().cpu() for v in net.vars.values()]).numpy()
+        if flat.size > DUMP_PER_NETWORK:
+            idx = np.sort(np.random.RandomState(DUMP_SAMPLE_SEED).choice(flat.size, DUMP_PER_NETWORK, replace=False))
+            flat = flat[idx]
+        np.save(os.path.join(directory, name + '.npy'), np.ascontiguousarray(flat, dtype=np.float32))
 
 
 def headline_shape_roofline(device, batch, reps=40, warm_s=0.4):
@@ -525,6 +549,8 @@ def main():
             info['drain']()
             barrier_sync()
             state['t_end'] = time.perf_counter()
+            if args.dump_outputs and rank == 0:     # untimed; the replicas of the other ranks are identical
+                dump_outputs(args.dump_outputs, {'G': info['G'], 'D': info['D'], 'Gs': info['Gs']})
             if profile_iters == 0:
                 return True
             # roofline leg: the same iterations with the graphs re-captured around device-side time stamps

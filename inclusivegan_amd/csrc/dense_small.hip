@@ -70,7 +70,7 @@ __global__ __launch_bounds__(256) void dense_small_kernel(DenseGroups G) {
     //     4-byte loads (below) they do not -- 0 of 1200 calls against 700-900 of 1000 (same probe).
     // The aggressor needs nothing but its main loop (barrier, LDS reads, matrix and vector instructions: no LDS-DMA, no store, no atomics: the probe's bisect),
     // so this is an interaction below the programming model, between co-resident waves of different processes; it cannot occur with one process per GPU, which
-    // is how the engine is deployed -- the eight-ranks-on-one-GPU runs are a test vehicle.  tests/test_gpu_dist.py::test_eight_rank_replay_stress guards it.
+    // is how the engine is deployed -- the several-ranks-on-one-GPU runs are a test vehicle.  tests/test_gpu_dist.py::test_shared_gpu_replay_stress guards it.
     constexpr unsigned OOB = 0x7FFFFFF0u;
     const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.x), 0, (int)(((unsigned)(M - 1) * (unsigned)a.ldx + (unsigned)K) * 4u), 0x00020000);
     const __amdgpu_buffer_rsrc_t rx2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.x2 ? a.x2 : a.x), 0, a.x2 ? (int)((unsigned)M * (unsigned)K * 4u) : 0, 0x00020000);

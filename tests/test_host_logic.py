@@ -294,3 +294,37 @@ def test_bench_evidence_plumbing():
         assert (traffic is not None and traffic > 0 and source.endswith(suffix)) or (traffic is None and 'collect_pmc' in source), (suffix, traffic, source)
     with open(b._latest_profile('pmc_dominant.json')) as f:
         assert b.family_of(json.load(f)['kernel']).startswith('conv_fwd_planes')
+
+
+def test_bench_dump_outputs_is_a_fixed_sample_within_64_mb(tmp_path):
+    """bench.py --dump-outputs (host side): a network with more values than DUMP_PER_NETWORK is written as a float32 sample of exactly that many of
+    its values, the same sample in every run; a smaller one is written whole, in its variables' order; three networks at the limit stay within
+    64 MB; the loop's global NumPy stream is left where it was."""
+    import importlib.util
+    import types
+    from collections import OrderedDict
+    spec = importlib.util.spec_from_file_location('bench_under_test', os.path.join(ROOT, 'bench.py'))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    n = b.DUMP_PER_NETWORK
+    g = torch.Generator().manual_seed(3)
+    big = types.SimpleNamespace(vars=OrderedDict([('a', torch.randn(n // 2, 3, generator=g)), ('b', torch.randn(7, generator=g)),
+                                                  ('c', torch.randn(n // 4, 2, generator=g))]))          # 2 n + 7 values
+    small = types.SimpleNamespace(vars=OrderedDict([('w', torch.randn(3, 5, generator=g)), ('b', torch.randn(5, generator=g))]))
+    nets = {'G': big, 'D': big, 'Gs': small}
+    np.random.seed(11)
+    before = np.random.get_state()
+    b.dump_outputs(str(tmp_path / 'first'), nets)
+    b.dump_outputs(str(tmp_path / 'second'), nets)
+    after = np.random.get_state()
+    assert np.array_equal(before[1], after[1]) and before[2] == after[2]
+    total = 0
+    for name in nets:
+        x, y = np.load(str(tmp_path / 'first' / (name + '.npy'))), np.load(str(tmp_path / 'second' / (name + '.npy')))
+        assert x.dtype == np.float32 and np.array_equal(x, y), name
+        total += os.path.getsize(str(tmp_path / 'first' / (name + '.npy')))
+    flat = torch.cat([v.reshape(-1) for v in big.vars.values()]).numpy()
+    sample = np.load(str(tmp_path / 'first' / 'G.npy'))
+    assert sample.shape == (n,) and np.isin(sample, flat).all() and not np.array_equal(sample, flat[:n])
+    assert np.array_equal(np.load(str(tmp_path / 'first' / 'Gs.npy')), torch.cat([v.reshape(-1) for v in small.vars.values()]).numpy())
+    assert total <= 3 * (4 * n + 1024) <= 64 * 10 ** 6
