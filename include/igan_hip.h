@@ -38,8 +38,9 @@ extern "C" {
  * 5 / 6: piece images and their sizes; 7: igan_conv_piece_form, igan_debug_f16_window; 8: the two-piece fp16 form scales every tensor per
  * pixel (forward / data gradient) or per channel (weight gradient) and writes its own images -- caller-written images (igan_to_pieces, x_pieces,
  * dy_pieces) belong to the bf16-piece form only; igan_conv2d_params gains x_colmax, igan_conv2d_wgrad_params x_colmax / dy_colmax at their ends;
- * 9: igan_conv2d_params gains w_pieces / w_pieces_bytes -- a caller-kept FILTER image for weights that never change (igan_filter_image_bytes, igan_filter_image)). */
-#define IGAN_ABI_VERSION 9
+ * 9: igan_conv2d_params gains w_pieces / w_pieces_bytes -- a caller-kept FILTER image for weights that never change (igan_filter_image_bytes, igan_filter_image);
+ * 10: igan_knn_radius_update, igan_manifold_member_update). */
+#define IGAN_ABI_VERSION 10
 
 typedef void* igan_stream_t; /* hipStream_t */
 
@@ -445,6 +446,37 @@ int igan_nn1_update(igan_stream_t stream, const float* query, const float* qnorm
                     const float* cand, const float* cnorm, double* best_d2, int* best_idx,
                     float* dots /* caller workspace, nq*nc floats */,
                     int nq, int nc, int dim, int idx_base);
+
+/* ------------------------------------------------------------------------
+ * Exact k-NN manifold search for the precision / recall metric (reference: metrics/precision_recall.py).
+ * Both entries take the products of one candidate batch from the exact-fp32 MFMA like igan_nn1_update
+ * (dots: caller workspace, nq*nc floats), screen with |q|^2 + |c|^2 - 2 q.c and its error interval (relative
+ * half-width 2^-22 * sqrt(dim) of |q|^2 + |c|^2) and measure every pair the interval cannot decide as a
+ * direct difference in fp64 -- the squared distance of igan_nn1_update, symmetric, 0 for identical rows.
+ * A non-finite exact distance counts as +infinity and is never within a radius.  Candidate batches may be
+ * streamed in any order; the results do not depend on it.  1 <= kcap <= 16, 1 <= nk <= 8; the operand
+ * limits are those of igan_conv2d.
+ *
+ * igan_knn_radius_update: folds the batch into each query's kcap smallest exact squared distances
+ * (kth_d2 [nq][kcap], ascending, a multiset: duplicates count; initialise to +infinity).  Fed every point of
+ * the query's own set, itself included, kth_d2[q][k] is what np.partition(distance_batch, seq)[:, k] leaves
+ * at 0-based position k (precision_recall.py:76,90), without the [10 000 x n] fp16 host block (:75).
+ *
+ * igan_manifold_member_update: sets member[q][s] = 1 (member [nq][nk]; initialise to 0; never cleared) when a
+ * candidate c of the batch has d2(q, c) <= cand_radius[c][s] (precision_recall.py:119-120, note the <=).
+ * A query already marked in every column skips the batch.
+ */
+int igan_knn_radius_update(igan_stream_t stream, const float* query, const float* qnorm,
+                           const float* cand, const float* cnorm,
+                           double* kth_d2 /* [nq][kcap] ascending, caller-initialised to +inf */,
+                           float* dots /* caller workspace, nq*nc floats */,
+                           int nq, int nc, int dim, int kcap);
+int igan_manifold_member_update(igan_stream_t stream, const float* query, const float* qnorm,
+                                const float* cand, const float* cnorm,
+                                const double* cand_radius /* [nc][nk] */,
+                                int* member /* [nq][nk], caller-initialised to 0 */,
+                                float* dots /* caller workspace, nq*nc floats */,
+                                int nq, int nc, int dim, int nk);
 
 /* ------------------------------------------------------------------------
  * Device-side time stamps (measurement support, not part of the reference's surface): igan_stamp writes the constant

@@ -117,7 +117,7 @@ class TapsParams(ctypes.Structure):
                 ('taps', ctypes.c_int), ('n', ctypes.c_int), ('scale', ctypes.c_float)]
 
 
-ABI_VERSION = 9      # include/igan_hip.h IGAN_ABI_VERSION
+ABI_VERSION = 10     # include/igan_hip.h IGAN_ABI_VERSION
 STRUCTS = (UpFirDn2DParams, FusedBiasActParams, Conv2DParams, Conv2DWgradParams, DenseParams, DenseWgradParams, TapsParams)   # igan_struct_size ids
 
 DENSE_MAX_GROUPS = 24
@@ -180,6 +180,8 @@ SIGNATURES = {
     'igan_mbstd_bwd': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I]),
     'igan_row_sqnorm': (_I, [_P, _P, _P, _I, _I]),
     'igan_nn1_update': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I]),
+    'igan_knn_radius_update': (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I]),
+    'igan_manifold_member_update': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I]),
     'igan_stamp': (_I, [_P, _P]),
     'igan_debug_set_conv_diag': (None, [_P]),
     'igan_stamp_accumulate': (_I, [_P, _P, _P, _I, _I]),

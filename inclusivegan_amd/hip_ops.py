@@ -1832,6 +1832,52 @@ def nn1_update_raw(query, qnorm, cand, cnorm, best_d2, best_idx, idx_base):
                                    nq, nc, dim, idx_base))
 
 
+def knn_radius_state(nq, kcap, device):
+    """Running state of igan_knn_radius_update for nq queries: the kcap smallest exact squared distances, fp64 [nq, kcap] = +inf."""
+    if not 1 <= int(kcap) <= 16:
+        raise ValueError('knn_radius_state: kcap must be in [1, 16]')
+    return torch.full((nq, int(kcap)), float('inf'), device=device, dtype=torch.float64)
+
+
+def knn_radius_update_raw(query, qnorm, cand, cnorm, kth_d2):
+    """Fold one candidate batch into the running kcap smallest exact squared distances (kth_d2 fp64 [nq, kcap] ascending; contiguous view)."""
+    lib = _abi.get_plugin()
+    _require_cuda_f32(query, qnorm, cand, cnorm)
+    if kth_d2.dtype != torch.float64 or not kth_d2.is_contiguous() or kth_d2.dim() != 2:
+        raise TypeError('knn_radius_update: kth_d2 must be contiguous float64 [nq, kcap]')
+    query = query.contiguous()
+    cand = cand.contiguous()
+    nq, dim = query.shape
+    nc = cand.shape[0]
+    if kth_d2.shape[0] != nq or cand.shape[1] != dim or qnorm.numel() != nq or cnorm.numel() != nc:
+        raise ValueError('knn_radius_update: shapes of query, cand, norms and kth_d2 do not agree')
+    dots = torch.empty((nq, nc), device=query.device, dtype=torch.float32)
+    _abi.check(lib.igan_knn_radius_update(_stream(), _ptr(query), _ptr(qnorm.contiguous()), _ptr(cand), _ptr(cnorm.contiguous()), _ptr(kth_d2), _ptr(dots),
+                                          nq, nc, dim, kth_d2.shape[1]))
+
+
+def manifold_member_update_raw(query, qnorm, cand, cnorm, cand_radius, member):
+    """Mark member[q, s] = 1 (int32 [nq, nk], contiguous view, starts at 0) when a candidate of the batch has an exact squared
+    distance <= cand_radius[c, s] (fp64 [nc, nk])."""
+    lib = _abi.get_plugin()
+    _require_cuda_f32(query, qnorm, cand, cnorm)
+    if cand_radius.dtype != torch.float64 or cand_radius.dim() != 2 or not cand_radius.is_cuda:
+        raise TypeError('manifold_member_update: cand_radius must be a device float64 [nc, nk]')
+    if member.dtype != torch.int32 or not member.is_contiguous() or member.dim() != 2:
+        raise TypeError('manifold_member_update: member must be contiguous int32 [nq, nk]')
+    query = query.contiguous()
+    cand = cand.contiguous()
+    cand_radius = cand_radius.contiguous()
+    nq, dim = query.shape
+    nc = cand.shape[0]
+    nk = member.shape[1]
+    if member.shape[0] != nq or tuple(cand_radius.shape) != (nc, nk) or cand.shape[1] != dim or qnorm.numel() != nq or cnorm.numel() != nc:
+        raise ValueError('manifold_member_update: shapes of query, cand, norms, cand_radius and member do not agree')
+    dots = torch.empty((nq, nc), device=query.device, dtype=torch.float32)
+    _abi.check(lib.igan_manifold_member_update(_stream(), _ptr(query), _ptr(qnorm.contiguous()), _ptr(cand), _ptr(cnorm.contiguous()), _ptr(cand_radius),
+                                               _ptr(member), _ptr(dots), nq, nc, dim, nk))
+
+
 def finite_check_raw(g, flag):
     lib = _abi.get_plugin()
     _abi.check(lib.igan_finite_check(_stream(), _ptr(g), g.numel(), _ptr(flag)))

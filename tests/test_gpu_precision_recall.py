@@ -1,0 +1,254 @@
+"""GPU: k-NN precision / recall on the exact HIP manifold search (csrc/knn_manifold.hip) against the values the reference's
+own ManifoldEstimator produced (tests/golden/pr_golden.npz) and against an fp64 brute force on the same fp32 features.
+Predictions and nearest indices are EQUAL on every row, not close; radii agree to the accuracy of an fp64 sum."""
+import numpy as np
+import pytest
+import torch
+
+from test_precision_recall import brute_evaluate, brute_manifold, brute_sqdist, load_golden
+
+pytestmark = pytest.mark.gpu
+
+RADIUS_RTOL = 1e-11      # an fp64 sum of <= 4096 terms is good to ~5e-13; the 1-NN tests use 1e-12 at dim 3072
+
+
+def PRM():
+    from inclusivegan_amd.metrics import precision_recall
+    return precision_recall
+
+
+def assert_realism_equal(got, want):
+    assert got.dtype == np.float32 and got.shape == want.shape
+    assert np.array_equal(np.isnan(got), np.isnan(want)) and np.array_equal(np.isposinf(got), np.isposinf(want))
+    finite = np.isfinite(want)
+    assert np.array_equal(got[finite], want[finite])
+
+
+@pytest.mark.parametrize('rows,cols', [(100, 128), (37, 61), (10000, 10000)])
+def test_golden_cases_equal_the_executed_reference(cuda_device, rows, cols):
+    pr = PRM()
+    z, cases = load_golden()
+    for c in cases:
+        ref, ev = z[c + '/ref'].astype(np.float32), z[c + '/eval'].astype(np.float32)
+        nhood = z[c + '/nhood_sizes'].tolist()
+        m = pr.ManifoldEstimator(None, ref, rows, cols, nhood)
+        assert m.D.dtype == np.float64 and np.array_equal(m.D, z[c + '/ref_radii'])
+        pred, realism, nearest = m.evaluate(ev, return_realism=True, return_neighbors=True)
+        assert pred.dtype == np.int32 and np.array_equal(pred, z[c + '/precision'])
+        assert nearest.dtype == np.int32 and np.array_equal(nearest, z[c + '/nearest'])
+        assert_realism_equal(realism, z[c + '/realism'])
+        # the other return shapes
+        assert np.array_equal(m.evaluate(ev), pred)
+        p2, r2 = m.evaluate(ev, return_realism=True)
+        p3, n3 = m.evaluate(ev, return_neighbors=True)
+        assert np.array_equal(p2, pred) and np.array_equal(p3, pred) and np.array_equal(n3, nearest)
+        assert_realism_equal(r2, z[c + '/realism'])
+        state = pr.knn_precision_recall_features(ref, ev, nhood_sizes=nhood, row_batch_size=rows, col_batch_size=cols)
+        assert np.array_equal(state.ref_manifold.D, z[c + '/ref_radii']) and np.array_equal(state.eval_manifold.D, z[c + '/eval_radii'])
+        assert np.array_equal(state.precision, z[c + '/precision']) and np.array_equal(state.recall, z[c + '/recall'])
+        assert np.array_equal(state.nearest_neighbors, z[c + '/nearest'])
+        assert_realism_equal(state.realism_scores, z[c + '/realism'])
+        assert np.array_equal(state.knn_precision, z[c + '/knn_precision']) and np.array_equal(state.knn_recall, z[c + '/knn_recall'])
+
+
+def real_valued_sets(dim, n_ref, n_eval, seed):
+    """Clustered reals, and evaluated points that are partly near them and partly far: both answers occur."""
+    rng = np.random.RandomState(seed)
+    centres = rng.randn(12, dim)
+    ref = (centres[rng.randint(0, 12, size=n_ref)] + 0.3 * rng.randn(n_ref, dim)).astype(np.float32)
+    near = ref[rng.randint(0, n_ref, size=n_eval // 2)] + (0.25 * rng.randn(n_eval // 2, dim)).astype(np.float32)
+    far = (1.5 * rng.randn(n_eval - n_eval // 2, dim)).astype(np.float32)
+    return ref, np.concatenate([near, far]).astype(np.float32)
+
+
+@pytest.mark.parametrize('dim,n_ref,n_eval', [(4096, 300, 260), (50, 333, 301)])
+def test_real_valued_features_equal_brute_force(cuda_device, dim, n_ref, n_eval):
+    pr = PRM()
+    nhood = [3, 5]
+    ref, ev = real_valued_sets(dim, n_ref, n_eval, seed=dim)
+    radii = brute_manifold(ref, nhood)
+    # a planted exact copy of the k-th neighbour of point 7 (test_boundary_point_is_inside_by_equality isolates the sphere of one point)
+    d7 = brute_sqdist(ref[7:8], ref)[0]
+    kth = int(np.argsort(d7, kind='stable')[nhood[0]])
+    ev[0] = ref[kth]
+    m = pr.ManifoldEstimator(None, ref, 128, 100, nhood)
+    assert m.D.shape == radii.shape
+    assert np.all(np.abs(m.D - radii) <= RADIUS_RTOL * radii), np.max(np.abs(m.D - radii) / radii)
+    pred, realism, nearest = m.evaluate(ev, return_realism=True, return_neighbors=True)
+    want_pred, want_realism, want_nearest = brute_evaluate(ref, radii, ev)
+    assert 0.1 < want_pred.mean() < 0.9
+    assert np.array_equal(pred, want_pred)
+    assert np.array_equal(nearest, want_nearest)
+    assert pred[0, 0] == 1 and nearest[0] == kth and np.isposinf(realism[0])
+    finite = np.isfinite(want_realism)
+    assert np.allclose(realism[finite], want_realism[finite], rtol=1e-6, atol=0)
+    # every point is inside its own manifold (d2(a, a) == 0 exactly)
+    own = m.evaluate(ref)
+    assert own.shape == (n_ref, 2) and own.min() == 1
+
+
+def test_boundary_point_is_inside_by_equality(cuda_device):
+    """A copy of the k-th neighbour of r0 sits exactly on the sphere of r0; with every other sphere switched off (radius -1: not
+    even its own centre counts) it is inside by `<=` and the symmetry of the exact distance alone, and the next neighbour is outside."""
+    pr = PRM()
+    rng = np.random.RandomState(3)
+    ref = rng.randn(40, 4096).astype(np.float32)
+    m = pr.ManifoldEstimator(None, ref, 16, 24, [3])
+    d0 = brute_sqdist(ref[:1], ref)[0]
+    order = np.argsort(d0, kind='stable')
+    kth, beyond = int(order[3]), int(order[4])
+    assert abs(m.D[0, 0] - d0[kth]) <= RADIUS_RTOL * d0[kth]
+    m.D[1:] = -1.0
+    pred = m.evaluate(np.stack([ref[kth], ref[beyond]]))
+    assert pred[0, 0] == 1 and pred[1, 0] == 0
+
+
+def test_useless_screening_still_exact(cuda_device):
+    """features = 100 + 1e-2 noise at dim 4096: |q|^2 ~ 4e7, so the screening interval (~1e3) dwarfs every distance (~1): every
+    pair is measured exactly, and the answers are still the brute force's."""
+    pr = PRM()
+    rng = np.random.RandomState(11)
+    ref = (100.0 + 1e-2 * rng.randn(200, 4096)).astype(np.float32)
+    ev = (100.0 + 1e-2 * rng.randn(150, 4096)).astype(np.float32)
+    ev[:60] = ref[:60] + (2e-3 * rng.randn(60, 4096)).astype(np.float32)
+    radii = brute_manifold(ref, [3])
+    m = pr.ManifoldEstimator(None, ref, 64, 96, [3])
+    assert np.all(np.abs(m.D - radii) <= RADIUS_RTOL * radii)
+    pred, nearest = m.evaluate(ev, return_neighbors=True)
+    want_pred, _, want_nearest = brute_evaluate(ref, radii, ev)
+    assert np.array_equal(pred, want_pred) and np.array_equal(nearest, want_nearest)
+    assert 0 < want_pred.sum() < want_pred.size
+
+
+@pytest.mark.parametrize('dim', [64, 50])
+def test_nan_rows_are_never_members_or_witnesses(cuda_device, dim):
+    pr = PRM()
+    ref, ev = real_valued_sets(dim, 150, 120, seed=5)
+    clean_m = pr.ManifoldEstimator(None, ref, 50, 64, [3])
+    clean_pred, clean_real, clean_near = clean_m.evaluate(ev, return_realism=True, return_neighbors=True)
+    # a NaN row among the evaluated: not a member; everyone else unchanged
+    ev_bad = ev.copy(); ev_bad[17, 3] = np.nan
+    pred, real, near = clean_m.evaluate(ev_bad, return_realism=True, return_neighbors=True)
+    keep = np.arange(ev.shape[0]) != 17
+    assert pred[17].max() == 0
+    assert np.array_equal(pred[keep], clean_pred[keep]) and np.array_equal(near[keep], clean_near[keep])
+    assert np.array_equal(real[keep], clean_real[keep], equal_nan=True)
+    want_pred, want_real, want_near = brute_evaluate(ref, clean_m.D, ev_bad)
+    assert np.array_equal(pred, want_pred) and np.array_equal(near, want_near)
+    assert np.allclose(real, want_real, rtol=1e-6, atol=0, equal_nan=True) and real[17] == 0       # x / inf
+    # a NaN row among the references: never a witness, never a neighbour; the manifold of the others is what brute force says
+    ref_bad = ref.copy(); ref_bad[9, dim - 1] = np.nan
+    m = pr.ManifoldEstimator(None, ref_bad, 50, 64, [3])
+    radii = brute_manifold(ref_bad, [3])
+    assert np.isposinf(m.D[9, 0]) and np.isposinf(radii[9, 0])
+    ok = np.arange(ref.shape[0]) != 9
+    assert np.all(np.abs(m.D[ok] - radii[ok]) <= RADIUS_RTOL * radii[ok])
+    pred, near = m.evaluate(ev, return_neighbors=True)
+    want_pred, _, want_near = brute_evaluate(ref_bad, radii, ev)
+    assert np.array_equal(pred, want_pred) and np.array_equal(near, want_near) and not (near == 9).any()
+    own = m.evaluate(ref_bad)
+    assert own[9, 0] == 0 and own[ok].min() == 1
+
+
+def test_tensor_and_numpy_inputs_and_batch_order(cuda_device):
+    from inclusivegan_amd import hip_ops
+    pr = PRM()
+    ref, ev = real_valued_sets(257, 230, 190, seed=9)
+    a = pr.knn_precision_recall_features(ref, ev, nhood_sizes=[3, 4], row_batch_size=70, col_batch_size=90)
+    b = pr.knn_precision_recall_features(torch.from_numpy(ref).to(cuda_device), torch.from_numpy(ev).to(cuda_device), nhood_sizes=[3, 4],
+                                         row_batch_size=70, col_batch_size=90)
+    for k in ('precision', 'recall', 'nearest_neighbors', 'knn_precision', 'knn_recall'):
+        assert np.array_equal(a[k], b[k]), k
+    assert np.array_equal(a.realism_scores, b.realism_scores, equal_nan=True)
+    assert np.array_equal(a.ref_manifold.D, b.ref_manifold.D) and np.array_equal(a.eval_manifold.D, b.eval_manifold.D)
+    # candidate batches streamed forwards and backwards leave the identical state, and so do other batch sizes
+    f = torch.from_numpy(ref).to(cuda_device)
+    n = hip_ops.row_sqnorm_raw(f)
+    states = []
+    for starts, step in ((range(0, 230, 64), 64), (reversed(range(0, 230, 64)), 64), (range(0, 230, 230), 230)):
+        st = hip_ops.knn_radius_state(230, 5, cuda_device)
+        for c0 in starts:
+            hip_ops.knn_radius_update_raw(f, n, f[c0:c0 + step], n[c0:c0 + step], st)
+        states.append(st.cpu().numpy())
+    assert np.array_equal(states[0], states[1]) and np.array_equal(states[0], states[2])
+    assert np.all(np.diff(states[0], axis=1) >= 0) and np.all(states[0][:, 0] == 0)
+    assert np.array_equal(states[0][:, [3, 4]], a.ref_manifold.D)
+    radii = torch.from_numpy(a.ref_manifold.D).to(cuda_device)
+    e = torch.from_numpy(ev).to(cuda_device)
+    en = hip_ops.row_sqnorm_raw(e)
+    flags = []
+    for starts in (range(0, 230, 64), reversed(range(0, 230, 64))):
+        member = torch.zeros(190, 2, device=cuda_device, dtype=torch.int32)
+        for c0 in starts:
+            hip_ops.manifold_member_update_raw(e, en, f[c0:c0 + 64], n[c0:c0 + 64], radii[c0:c0 + 64], member)
+        flags.append(member.cpu().numpy())
+    assert np.array_equal(flags[0], flags[1]) and np.array_equal(flags[0], a.precision)
+    # a flag is never cleared: a batch with no witness leaves set flags alone
+    member = torch.ones(190, 2, device=cuda_device, dtype=torch.int32)
+    hip_ops.manifold_member_update_raw(e, en, f[:64], n[:64], torch.zeros(64, 2, device=cuda_device, dtype=torch.float64), member)
+    assert int(member.min()) == 1
+
+
+def test_estimator_rejects_what_it_cannot_compute(cuda_device):
+    pr = PRM()
+    ref = np.zeros((4, 8), np.float32)
+    with pytest.raises(ValueError):
+        pr.ManifoldEstimator(None, ref, 4, 4, [4])              # n > max(nhood_sizes) is required
+    m = pr.ManifoldEstimator(None, ref, 4, 4, [3])              # four identical points: every radius is 0, 0 / 0 realism is nan
+    assert np.array_equal(m.D, np.zeros((4, 1)))
+    pred, realism, nearest = m.evaluate(ref[:2], return_realism=True, return_neighbors=True)
+    assert pred.min() == 1 and np.isnan(realism).all() and np.array_equal(nearest, [0, 0])
+    # clamp_to_percentile: radii above the percentile of their column become 0 (reference :92-94)
+    feats, _ = real_valued_sets(32, 120, 2, seed=2)
+    full = pr.ManifoldEstimator(None, feats, 50, 50, [3, 5])
+    clamped = pr.ManifoldEstimator(None, feats, 50, 50, [3, 5], clamp_to_percentile=50)
+    want = full.D.copy()
+    want[want > np.percentile(full.D, 50, axis=0)] = 0
+    assert np.array_equal(clamped.D, want) and (clamped.D == 0).sum() >= 100
+    # the reference's distance surface is still there
+    u, v = torch.from_numpy(feats[:5]).to(cuda_device), torch.from_numpy(feats[5:12]).to(cuda_device)
+    d = pr.batch_pairwise_distances(u, v)
+    assert d.dtype == torch.float32 and d.shape == (5, 7) and float(d.min()) >= 0
+    assert np.allclose(d.cpu().numpy(), brute_sqdist(feats[:5], feats[5:12]), rtol=1e-4, atol=1e-3)
+    assert np.allclose(pr.DistanceBlock(32, 1).pairwise_distances(feats[:5], feats[5:12]), d.cpu().numpy())
+
+
+def test_pr_metric_on_the_hip_generator(cuda_device):
+    """PR end to end: reals from the synthetic data set, fakes from Gs on the HIP path, injected feature network (a fixed random
+    projection of the uint8 image); the two reported numbers equal knn_precision_recall_features on the very same features."""
+    from inclusivegan_amd.dnnlib import tflib
+    pr = PRM()
+    dev = cuda_device
+    Gs = tflib.Network('Gs', func_name='inclusivegan_amd.training.networks_stylegan2.G_main', architecture='skip', num_channels=3,
+                       resolution=32, label_size=0, fmap_base=512, device=dev, seed=5)
+    proj = torch.randn(3 * 32 * 32, 24, device=dev, generator=torch.Generator(device=dev).manual_seed(1)) / 55.0
+    seen = dict(real=[], fake=[], real_done=False)
+
+    def feature_fn(images):
+        assert images.dtype == torch.uint8 and tuple(images.shape[1:]) == (3, 32, 32) and images.is_cuda
+        f = images.float().reshape(images.shape[0], -1) @ proj
+        seen['fake' if seen['real_done'] else 'real'].append(f.cpu().numpy())
+        return f
+
+    n = 200
+    m = pr.PR(num_images=n, nhood_size=3, minibatch_per_gpu=32, row_batch_size=64, col_batch_size=64, feature_fn=feature_fn, name='pr200')
+    orig = m._generate
+    m._generate = lambda *a, **k: (seen.__setitem__('real_done', True), orig(*a, **k))[1]
+    m.run(Gs, dataset_args=dict(resolution=32, num_channels=3, label_size=0, data_size=256), mirror_augment=False, log_results=False)
+    assert [r.suffix for r in m._results] == ['_precision', '_recall']
+    values = [float(r.value) for r in m._results]
+    assert all(0.0 <= v <= 1.0 for v in values)
+    real, fake = np.concatenate(seen['real'])[:n], np.concatenate(seen['fake'])[:n]
+    assert real.shape == (n, 24) and fake.shape == (n, 24)
+    state = pr.knn_precision_recall_features(real, fake, nhood_sizes=[3], row_batch_size=64, col_batch_size=64)
+    assert values == [float(state.knn_precision[0]), float(state.knn_recall[0])]
+    radii = brute_manifold(real, [3])
+    want_pred, _, _ = brute_evaluate(real, radii, fake)
+    assert np.array_equal(state.precision, want_pred)
+    assert 'pr200_precision' in m.get_result_str() and 'pr200_recall' in m.get_result_str()
+    # real features are cached per object: a second run asks the feature network for fakes only
+    calls = len(seen['real'])
+    m._generate = orig
+    seen['real_done'] = True
+    m.run(Gs, dataset_args=dict(resolution=32, num_channels=3, label_size=0, data_size=256), mirror_augment=False, log_results=False)
+    assert len(seen['real']) == calls and len(m._results) == 2
