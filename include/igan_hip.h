@@ -479,6 +479,32 @@ int igan_manifold_member_update(igan_stream_t stream, const float* query, const 
                                 int nq, int nc, int dim, int nk);
 
 /* ------------------------------------------------------------------------
+ * Perceptual path length (reference: metrics/perceptual_path_length.py; ppl_zfull .. ppl2_wend).  Added without a
+ * version bump: two more exports, no struct or signature changes.
+ *
+ * igan_ppl_endpoints replaces normalize / slerp (:19-30) and the endpoint expressions (:59-77): for pair i with ends
+ * lat[2i], lat[2i+1] ([2n][dim] fp32) and position t[i] it writes the point at t[i] to out[2i] and the point at
+ * t[i] + epsilon to out[2i+1] -- the interleaving of :71,76.  mode 0: lerp a + (b - a) * t (dim = num_layers *
+ * dlatent_size); mode 1: the reference's slerp (three normalisations, acos, cos, sin).  The arithmetic is fp64 from the
+ * fp32 inputs, t + epsilon included, and each output is rounded to fp32 once: the two rows of a pair differ by about
+ * epsilon of their size and the metric divides by epsilon^2, so an fp32 evaluation would put ~1e-3 relative error into
+ * the difference before G runs.  lerp is three uncontracted fp64 operations (numpy's result bit for bit).  Degenerate
+ * pairs (a parallel to b, a zero row) give what the formula gives, NaN included, as in the reference.  Any dim >= 1;
+ * 16-byte accesses when dim % 4 == 0 and both buffers are 16-byte aligned.  out must not overlap lat.
+ *
+ * igan_ppl_crop_prep replaces :84-96 (crop, box-mean downsample, range change) in one pass.  x is G's fp32 image batch
+ * addressed through ELEMENT STRIDES, x[n][c][h][w] at n*stride_n + c*stride_c + h*stride_h + w*stride_w, so whatever
+ * layout G_synthesis hands back is read in place.  The window is rows y0:y1, columns x0:x1; factor >= 1 divides both
+ * sides.  y is [N][(y1-y0)/factor][(x1-x0)/factor][C] channel-minor, 16-byte aligned:
+ *     y = (m + 1) * (255 / 2),   m = (sum of the factor x factor box in fp32, rows then columns) * (1 / factor^2)
+ * uncontracted and without a clamp (the reference has none); factor == 1 gives fp32 (x + 1) * 127.5 bit for bit. */
+int igan_ppl_endpoints(igan_stream_t stream, const float* lat, const float* t, float* out, int n, int dim,
+                       double epsilon, int mode);
+int igan_ppl_crop_prep(igan_stream_t stream, const float* x, float* y, int N, int C, int H, int W,
+                       int y0, int y1, int x0, int x1, int factor,
+                       long long stride_n, long long stride_c, long long stride_h, long long stride_w);
+
+/* ------------------------------------------------------------------------
  * Device-side time stamps (measurement support, not part of the reference's surface): igan_stamp writes the constant
  * 100 MHz counter (10 ns ticks) into *slot in stream order, so two stamps bracket whatever was launched between them --
  * also inside a captured hipGraph, where host events cannot be placed.  igan_stamp_accumulate adds, for pairs

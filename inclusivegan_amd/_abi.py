@@ -124,7 +124,7 @@ DENSE_MAX_GROUPS = 24
 DENSE_PRO_NONE, DENSE_PRO_SQUARE, DENSE_PRO_DEMOD_GRAD = 0, 1, 2
 DENSE_EPI_SCALE, DENSE_EPI_BIAS, DENSE_EPI_RSQRT, DENSE_EPI_STYLE_GRAD = 0, 1, 2, 3
 
-_I, _F, _P, _SZ = ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t
+_I, _F, _P, _SZ, _LL = ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_longlong
 
 # name -> (restype, argtypes): every symbol include/igan_hip.h declares.
 SIGNATURES = {
@@ -182,6 +182,8 @@ SIGNATURES = {
     'igan_nn1_update': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I]),
     'igan_knn_radius_update': (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I]),
     'igan_manifold_member_update': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I]),
+    'igan_ppl_endpoints': (_I, [_P, _P, _P, _P, _I, _I, ctypes.c_double, _I]),
+    'igan_ppl_crop_prep': (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _LL, _LL, _LL, _LL]),
     'igan_stamp': (_I, [_P, _P]),
     'igan_debug_set_conv_diag': (None, [_P]),
     'igan_stamp_accumulate': (_I, [_P, _P, _P, _I, _I]),

@@ -222,6 +222,10 @@ _random = _DefaultRandom()
 def random_source():
     return _random
 
+def default_random():
+    """A fresh default source: `with use_random(default_random())` shields draws that are not part of a recorded / replayed run."""
+    return _DefaultRandom()
+
 @contextlib.contextmanager
 def use_random(source):
     global _random

@@ -1707,6 +1707,51 @@ class LpipsPairsFn(torch.autograd.Function):
         return (None,) * L + tuple(outs) + (None,) * L + (None, None)
 
 
+_adjacent_tables = {}
+
+
+def _lpips_adjacent_tables(n, device):
+    """int32 sample tables (2i, 2i + 1) of the n adjacent pairs of one interleaved batch, created once per (n, device)."""
+    key = (n, str(device))
+    if key not in _adjacent_tables:
+        ia = (2 * np.arange(n)).astype(np.int32)
+        _adjacent_tables[key] = (torch.from_numpy(ia).to(device), torch.from_numpy(ia + 1).to(device))
+    return _adjacent_tables[key]
+
+
+def lpips_adjacent_pairs_raw(feats, lins):
+    """LPIPS distance of every (row 2i, row 2i + 1) pair of ONE feature batch (perceptual_path_length.py:99-101: img_e0 =
+    images[0::2], img_e1 = images[1::2]) -> [n].  feats: per layer [2n, C, H, W] raw VGG features of the interleaved images,
+    lins: per layer [C] = |lin| / (C * H * W).  Forward only.  igan_lpips_pairs_fwd reads both sides of a pair from the same
+    tensor through a sample table of its own, so the 2n images go through VGG once and nothing is de-interleaved by copy."""
+    lib = _abi.get_plugin()
+    _require_cuda_f32(*feats, *lins)
+    feats = [nhwc(t) for t in feats]
+    lins = [t.contiguous() for t in lins]
+    if len(feats) != len(lins) or not feats:
+        raise ValueError('lpips_adjacent_pairs: one lin weight vector per feature layer')
+    two_n = int(feats[0].shape[0])
+    if two_n < 2 or two_n % 2:
+        raise ValueError('lpips_adjacent_pairs: the batch holds pairs in adjacent rows, its size must be even (got %d)' % two_n)
+    n = two_n // 2
+    ia, ib = _lpips_adjacent_tables(n, feats[0].device)
+    geo = []
+    for f, lin in zip(feats, lins):
+        if f.dim() != 4 or f.shape[0] != two_n or lin.numel() != f.shape[1]:
+            raise ValueError('lpips_adjacent_pairs: feature layers must be [2n, C, H, W] with lin [C]')
+        c, hw = int(f.shape[1]), int(f.shape[2] * f.shape[3])
+        geo.append((c, hw, lib.igan_lpips_layer_blocks(n, hw)))
+    width = sum(g[2] for g in geo)
+    partial = torch.empty((n, width), device=feats[0].device, dtype=torch.float32)
+    col = 0
+    st = _stream()
+    for f, lin, (c, hw, blocks) in zip(feats, lins, geo):
+        _abi.check(lib.igan_lpips_pairs_fwd(st, _ptr(f), _ptr(f), _ptr(lin), _ptr(ia), _ptr(ib), partial.data_ptr() + 4 * col,
+                                            width, blocks, n, hw, c))
+        col += blocks
+    return partial.sum(dim=1)
+
+
 class PoolTapFn(torch.autograd.Function):
     """x -> (x, maxpool2x2(x)): a VGG feature map that is both an LPIPS tap and the input of the next block.  One Function
     owns both consumers so that the backward is one pass, dx = d_tap + route(d_pooled) (igan_maxpool2x2_bwd), instead of a
@@ -1800,7 +1845,7 @@ class MbStdFn(torch.autograd.Function):
 
 
 # ----------------------------------------------------------------------------
-# nearest neighbour, optimizer
+# nearest neighbour
 
 def row_sqnorm_raw(a):
     lib = _abi.get_plugin()
@@ -1877,6 +1922,47 @@ def manifold_member_update_raw(query, qnorm, cand, cnorm, cand_radius, member):
     _abi.check(lib.igan_manifold_member_update(_stream(), _ptr(query), _ptr(qnorm.contiguous()), _ptr(cand), _ptr(cnorm.contiguous()), _ptr(cand_radius),
                                                _ptr(member), _ptr(dots), nq, nc, dim, nk))
 
+
+# ----------------------------------------------------------------------------
+# perceptual path length
+
+def ppl_endpoints_raw(lat, t, epsilon, mode):
+    """The two path endpoints of every pair (perceptual_path_length.py:59-77): lat [2n, ...] (rows 2i, 2i + 1 the ends of pair
+    i; trailing axes are flattened), t [n] -> same shape as lat, row 2i at t[i], row 2i + 1 at t[i] + epsilon.  mode 0 = lerp,
+    1 = slerp; fp64 inside, one rounding to fp32 (igan_ppl_endpoints)."""
+    lib = _abi.get_plugin()
+    _require_cuda_f32(lat, t)
+    if lat.dim() < 2 or lat.shape[0] % 2 or t.dim() != 1 or 2 * t.shape[0] != lat.shape[0]:
+        raise ValueError('ppl_endpoints: lat must be [2n, ...] and t [n] (got %s and %s)' % (tuple(lat.shape), tuple(t.shape)))
+    lat = lat.contiguous()
+    t = t.contiguous()
+    n = int(t.shape[0])
+    dim = int(lat.numel() // max(2 * n, 1))
+    out = torch.empty_like(lat)
+    _abi.check(lib.igan_ppl_endpoints(_stream(), _ptr(lat), _ptr(t), _ptr(out), n, dim, float(epsilon), int(mode)))
+    return out
+
+
+def ppl_crop_prep_raw(images, window, factor):
+    """Crop to window = (y0, y1, x0, x1), box-mean downsample by `factor` and map [-1, 1] to [0, 255]
+    (perceptual_path_length.py:84-96) in one pass over images [N, C, H, W] in whatever strides they have -> [N, C, h, w]
+    channels_last, the layout lpips.vgg_features runs on."""
+    lib = _abi.get_plugin()
+    _require_cuda_f32(images)
+    if images.dim() != 4:
+        raise ValueError('ppl_crop_prep: images must be [N, C, H, W]')
+    y0, y1, x0, x1 = (int(v) for v in window)
+    factor = int(factor)
+    n, c, h, w = (int(v) for v in images.shape)
+    oh, ow = max(y1 - y0, 0) // max(factor, 1), max(x1 - x0, 0) // max(factor, 1)
+    out = empty_nchw(n, c, oh, ow, images)
+    sn, sc, sh, sw = (int(v) for v in images.stride())
+    _abi.check(lib.igan_ppl_crop_prep(_stream(), _ptr(images), _ptr(out), n, c, h, w, y0, y1, x0, x1, factor, sn, sc, sh, sw))
+    return out
+
+
+# ----------------------------------------------------------------------------
+# optimizer
 
 def finite_check_raw(g, flag):
     lib = _abi.get_plugin()

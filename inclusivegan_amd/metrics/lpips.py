@@ -136,6 +136,13 @@ def pair_distances(feats_gen, feats_real, n):
     return d.view(4, n).unbind(0)
 
 
+def adjacent_pair_distances(feats):
+    """Distances d(image 2i, image 2i + 1) on the features of ONE interleaved batch of 2n images -> [n]
+    (perceptual_path_length.py:99-101); forward only, no de-interleaving copies."""
+    lins = [_lin_weights(i, int(f.shape[1]), int(f.shape[2] * f.shape[3])) for i, f in enumerate(feats)]
+    return hip_ops.lpips_adjacent_pairs_raw(feats, lins)
+
+
 def vgg16_zhang_perceptual(images_a, images_b, resolution=64, **_kwargs):
     """Build function: LPIPS distance between two image batches in [0,255] -> [N]."""
     return feature_distance(vgg_features(images_a), vgg_features(images_b))
@@ -156,3 +163,8 @@ def distance_of(lpips_net, feats_a, feats_b):
 def pair_distances_of(lpips_net, feats_gen, feats_real, n):
     with tfutil.variable_store(lpips_net):
         return pair_distances(feats_gen, feats_real, n)
+
+
+def adjacent_pair_distances_of(lpips_net, feats):
+    with tfutil.variable_store(lpips_net):
+        return adjacent_pair_distances(feats)
