@@ -42,7 +42,9 @@ def fused_bias_act(x, b=None, axis=1, act='linear', alpha=None, gain=None):
 
 
 def fused_bias_act_kernel_ref(x, b, ref, grad, act_idx, alpha, gain, step_b):
-    """Element-wise restatement of FusedBiasActKernel (fused_bias_act.cu:50-115) on flat tensors."""
+    """Element-wise restatement of FusedBiasActKernel (fused_bias_act.cu:50-115) on flat tensors, in the dtype of x, with the kernel's
+    range clamps (expRange = 80, halfExpRange = 40: tanh, sigmoid, softplus, swish and swish's gradient forms) and its selects as written:
+    a comparison with NaN is false, so relu(NaN) = 0 while lrelu(NaN) = NaN * alpha = NaN (tests/test_nonfinite_cases.py pins both)."""
     x = x.reshape(-1).clone()
     n = x.numel()
     if b is not None:
@@ -52,6 +54,7 @@ def fused_bias_act_kernel_ref(x, b, ref, grad, act_idx, alpha, gain, step_b):
     if gain != 0.0 and act_idx != 9:
         r = r / gain
     sel = act_idx * 10 + grad
+    expRange, halfExpRange = 80.0, 40.0
     seluScale = 1.0507009873554804934193349852946
     seluAlpha = 1.6732632423543772848170429916717
     if sel in (10, 11): y = x
@@ -60,10 +63,10 @@ def fused_bias_act_kernel_ref(x, b, ref, grad, act_idx, alpha, gain, step_b):
     elif sel == 21: y = torch.where(r > 0, x, torch.zeros_like(x))
     elif sel == 30: y = torch.where(x > 0, x, x * alpha)
     elif sel == 31: y = torch.where(r > 0, x, x * alpha)
-    elif sel == 40: y = torch.tanh(x)
+    elif sel == 40: y = torch.where(x < -expRange, -torch.ones_like(x), torch.where(x > expRange, torch.ones_like(x), torch.tanh(x)))
     elif sel == 41: y = x * (1 - r * r)
     elif sel == 42: y = x * (1 - r * r) * (-2 * r)
-    elif sel == 50: y = torch.sigmoid(x)
+    elif sel == 50: y = torch.where(x < -expRange, torch.zeros_like(x), torch.sigmoid(x))
     elif sel == 51: y = x * r * (1 - r)
     elif sel == 52: y = x * r * (1 - r) * (1 - 2 * r)
     elif sel == 60: y = torch.where(x >= 0, x, torch.exp(x) - 1)
@@ -72,11 +75,11 @@ def fused_bias_act_kernel_ref(x, b, ref, grad, act_idx, alpha, gain, step_b):
     elif sel == 70: y = torch.where(x >= 0, seluScale * x, (seluScale * seluAlpha) * (torch.exp(x) - 1))
     elif sel == 71: y = torch.where(r >= 0, x * seluScale, x * (r + seluScale * seluAlpha))
     elif sel == 72: y = torch.where(r >= 0, torch.zeros_like(x), x * (r + seluScale * seluAlpha))
-    elif sel == 80: y = F.softplus(x)
+    elif sel == 80: y = torch.where(x > expRange, x, F.softplus(x))
     elif sel == 81: y = x * (1 - torch.exp(-r))
     elif sel == 82: c = torch.exp(-r); y = x * c * (1 - c)
-    elif sel == 90: y = x * torch.sigmoid(x)
-    elif sel == 91: c = torch.exp(r); d = c + 1; y = x * c * (r + d) / (d * d)
-    elif sel == 92: c = torch.exp(r); d = c + 1; y = x * c * (r * (2 - d) + 2 * d) / (d * d * d)
+    elif sel == 90: y = torch.where(x < -expRange, torch.zeros_like(x), x * torch.sigmoid(x))
+    elif sel == 91: c = torch.exp(r); d = c + 1; y = torch.where(r > halfExpRange, x, x * c * (r + d) / (d * d))
+    elif sel == 92: c = torch.exp(r); d = c + 1; y = torch.where(r > halfExpRange, torch.zeros_like(x), x * c * (r * (2 - d) + 2 * d) / (d * d * d))
     else: y = x
     return y * gain
