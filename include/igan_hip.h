@@ -39,7 +39,8 @@ extern "C" {
  * pixel (forward / data gradient) or per channel (weight gradient) and writes its own images -- caller-written images (igan_to_pieces, x_pieces,
  * dy_pieces) belong to the bf16-piece form only; igan_conv2d_params gains x_colmax, igan_conv2d_wgrad_params x_colmax / dy_colmax at their ends;
  * 9: igan_conv2d_params gains w_pieces / w_pieces_bytes -- a caller-kept FILTER image for weights that never change (igan_filter_image_bytes, igan_filter_image);
- * 10: igan_knn_radius_update, igan_manifold_member_update). */
+ * 10: igan_knn_radius_update, igan_manifold_member_update; added under 10 without a bump, exports only: igan_ppl_endpoints, igan_ppl_crop_prep,
+ * igan_linear_svc_workspace_bytes, igan_linear_svc_grad, igan_linear_svc_hv, igan_linear_svc_linesearch, igan_linear_svc_predict). */
 #define IGAN_ABI_VERSION 10
 
 typedef void* igan_stream_t; /* hipStream_t */
@@ -503,6 +504,39 @@ int igan_ppl_endpoints(igan_stream_t stream, const float* lat, const float* t, f
 int igan_ppl_crop_prep(igan_stream_t stream, const float* x, float* y, int N, int C, int H, int W,
                        int y0, int y1, int x0, int x1, int factor,
                        long long stride_n, long long stride_c, long long stride_h, long long stride_w);
+
+/* ------------------------------------------------------------------------
+ * Batched primal linear SVM for the linear separability metric (reference: metrics/linear_separability.py:162-165,
+ * sklearn.svm.LinearSVC() at its defaults: squared hinge, L2, C = 1, the bias a regularised extra feature of value 1).
+ * Added without a version bump: more exports, no struct or signature changes.
+ *
+ *     f_a(w) = 1/2 |w|^2 + C * sum_{i : Y[i][a] != 0} max(0, 1 - Y[i][a] * w.(x_i, 1))^2        w in R^(F+1), bias last
+ *
+ * X [n][F] fp32 row-major is shared by all A attributes; Y [n][A] int8 holds -1 / +1, 0 = the attribute has pruned the
+ * sample.  1 <= A <= 64 per launch (larger sets go in groups), 1 <= F <= 1024 (IGAN_ERR_UNSUPPORTED beyond either),
+ * n * F * 4 below 2 GiB and n * A within int32 (IGAN_ERR_INVALID_ARGUMENT).  Arguments are validated before anything
+ * touches a device.  One pass reads X from HBM once and uses each 32-row slab for both products on the exact-fp32 MFMA;
+ * sums over n are per-workgroup partials added in a fixed order in fp64 -- no atomics, the same inputs give the same bits.
+ * workspace: igan_linear_svc_workspace_bytes(n, F, A) bytes (0 for sizes outside the limits), contents irrelevant.
+ *
+ * igan_linear_svc_grad (:162-163, the fit): dec[i][a] = W[a].(x_i, 1); m = 1 - y dec; active[i][a] = (y != 0 && m > 0);
+ *     loss[a] = sum of m^2 over active samples; grad[a] = -2C * sum_i active y m (x_i, 1)   (the caller adds W[a]).
+ * igan_linear_svc_hv (:162-163): z[i][a] = S[a].(x_i, 1); hv[a] = 2C * sum_i active z (x_i, 1)   (the caller adds S[a]);
+ *     active is the mask the last igan_linear_svc_grad stored.
+ * igan_linear_svc_linesearch (:162-163): out[k][a] = sum_{y != 0} max(0, 1 - y (dec + t[k][a] z))^2 for 1 <= T <= 8 step
+ *     sizes per attribute, from dec and z alone (dec(w + t s) = dec(w) + t z), evaluated in fp64; X is not read.
+ * igan_linear_svc_predict (:164-165, score / predict): pred[i][a] = (dec[i][a] > 0). */
+size_t igan_linear_svc_workspace_bytes(int n, int F, int A);
+int igan_linear_svc_grad(igan_stream_t stream, const float* X, const signed char* Y, const float* W /* [A][F+1] */,
+                         float* dec /* [n][A] */, unsigned char* active /* [n][A] */, double* loss /* [A] */,
+                         double* grad /* [A][F+1] */, void* workspace, size_t workspace_bytes, int n, int F, int A, double C);
+int igan_linear_svc_hv(igan_stream_t stream, const float* X, const unsigned char* active, const float* S /* [A][F+1] */,
+                       float* z /* [n][A] */, double* hv /* [A][F+1] */, void* workspace, size_t workspace_bytes,
+                       int n, int F, int A, double C);
+int igan_linear_svc_linesearch(igan_stream_t stream, const float* dec, const float* z, const signed char* Y,
+                               const double* t /* [T][A] */, double* out /* [T][A] */, void* workspace, size_t workspace_bytes,
+                               int n, int A, int T);
+int igan_linear_svc_predict(igan_stream_t stream, const float* dec, int* pred /* [n][A] */, int n, int A);
 
 /* ------------------------------------------------------------------------
  * Device-side time stamps (measurement support, not part of the reference's surface): igan_stamp writes the constant

@@ -184,6 +184,11 @@ SIGNATURES = {
     'igan_manifold_member_update': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I]),
     'igan_ppl_endpoints': (_I, [_P, _P, _P, _P, _I, _I, ctypes.c_double, _I]),
     'igan_ppl_crop_prep': (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _LL, _LL, _LL, _LL]),
+    'igan_linear_svc_workspace_bytes': (_SZ, [_I, _I, _I]),
+    'igan_linear_svc_grad': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _I, _I, _I, ctypes.c_double]),
+    'igan_linear_svc_hv': (_I, [_P, _P, _P, _P, _P, _P, _P, _SZ, _I, _I, _I, ctypes.c_double]),
+    'igan_linear_svc_linesearch': (_I, [_P, _P, _P, _P, _P, _P, _P, _SZ, _I, _I, _I]),
+    'igan_linear_svc_predict': (_I, [_P, _P, _P, _I, _I]),
     'igan_stamp': (_I, [_P, _P]),
     'igan_debug_set_conv_diag': (None, [_P]),
     'igan_stamp_accumulate': (_I, [_P, _P, _P, _I, _I]),

@@ -1978,3 +1978,91 @@ def adam_step_raw(w, g, m, v, lr, beta1, beta2, eps, pow_state, skip_flag):
 def ema_raw(dst, src, beta):
     lib = _abi.get_plugin()
     _abi.check(lib.igan_ema(_stream(), _ptr(dst), _ptr(src), dst.numel(), float(beta)))
+
+
+# ---- batched primal linear SVM (csrc/linear_svc.hip; the linear separability metric) ----------------------------------------
+LINEAR_SVC_MAX_ATTRIBUTES = 64      # per launch
+LINEAR_SVC_MAX_FEATURES = 1024
+LINEAR_SVC_MAX_STEPS = 8            # step sizes per line-search call
+
+
+def _require_svc(name, *specs):
+    """specs: (tensor, dtype, description) -- every operand is a contiguous device tensor of exactly that type."""
+    for t, dtype, what in specs:
+        if not t.is_cuda:
+            raise RuntimeError('inclusivegan_amd kernels need tensors on a ROCm device (got %s); there is no CPU path' % t.device)
+        if t.dtype != dtype or not t.is_contiguous():
+            raise TypeError('%s: %s must be contiguous %s (got %s%s)' % (name, what, dtype, t.dtype, '' if t.is_contiguous() else ', strided'))
+
+
+def linear_svc_workspace(n, F, A, device):
+    """Scratch for the three reducing entry points at these sizes (contents irrelevant, reusable across calls)."""
+    nbytes = int(_abi.get_plugin().igan_linear_svc_workspace_bytes(int(n), int(F), int(A)))
+    if nbytes == 0:
+        raise NotImplementedError('linear_svc: n >= 1, 1 <= F <= %d and 1 <= A <= %d per launch (got n %d, F %d, A %d)'
+                                  % (LINEAR_SVC_MAX_FEATURES, LINEAR_SVC_MAX_ATTRIBUTES, n, F, A))
+    return torch.empty((nbytes + 7) // 8, device=device, dtype=torch.float64)
+
+
+def linear_svc_grad_raw(X, Y, W, dec, active, C=1.0, workspace=None):
+    """One pass over X [n, F] for all A attributes at W [A, F + 1] fp32 (bias last): writes dec fp32 [n, A] and the active mask
+    uint8 [n, A], returns (loss fp64 [A] = sum of m^2 over active samples, grad fp64 [A, F + 1] = -2C X^T(y m active); the
+    caller adds W).  Y int8 [n, A]: -1 / +1, 0 = pruned."""
+    lib = _abi.get_plugin()
+    _require_svc('linear_svc_grad', (X, torch.float32, 'X'), (Y, torch.int8, 'Y'), (W, torch.float32, 'W'), (dec, torch.float32, 'dec'),
+                 (active, torch.uint8, 'active'))
+    if X.dim() != 2 or Y.dim() != 2:
+        raise ValueError('linear_svc_grad: X must be [n, F] and Y [n, A]')
+    (n, F), A = X.shape, Y.shape[1]
+    if Y.shape[0] != n or tuple(W.shape) != (A, F + 1) or tuple(dec.shape) != (n, A) or tuple(active.shape) != (n, A):
+        raise ValueError('linear_svc_grad: shapes of X, Y, W, dec and active do not agree')
+    ws = linear_svc_workspace(n, F, A, X.device) if workspace is None else workspace
+    loss = torch.empty(A, device=X.device, dtype=torch.float64)
+    grad = torch.empty((A, F + 1), device=X.device, dtype=torch.float64)
+    _abi.check(lib.igan_linear_svc_grad(_stream(), _ptr(X), _ptr(Y), _ptr(W), _ptr(dec), _ptr(active), _ptr(loss), _ptr(grad), _ptr(ws),
+                                        ws.numel() * ws.element_size(), n, F, A, float(C)))
+    return loss, grad
+
+
+def linear_svc_hv_raw(X, active, S, z, C=1.0, workspace=None):
+    """One pass over X for all A attributes at S [A, F + 1] fp32: writes z fp32 [n, A] = S.(x, 1), returns fp64 [A, F + 1] =
+    2C X^T(active z) (the caller adds S).  `active` is the mask the last gradient pass stored."""
+    lib = _abi.get_plugin()
+    _require_svc('linear_svc_hv', (X, torch.float32, 'X'), (active, torch.uint8, 'active'), (S, torch.float32, 'S'), (z, torch.float32, 'z'))
+    if X.dim() != 2 or active.dim() != 2:
+        raise ValueError('linear_svc_hv: X must be [n, F] and active [n, A]')
+    (n, F), A = X.shape, active.shape[1]
+    if active.shape[0] != n or tuple(S.shape) != (A, F + 1) or tuple(z.shape) != (n, A):
+        raise ValueError('linear_svc_hv: shapes of X, active, S and z do not agree')
+    ws = linear_svc_workspace(n, F, A, X.device) if workspace is None else workspace
+    hv = torch.empty((A, F + 1), device=X.device, dtype=torch.float64)
+    _abi.check(lib.igan_linear_svc_hv(_stream(), _ptr(X), _ptr(active), _ptr(S), _ptr(z), _ptr(hv), _ptr(ws), ws.numel() * ws.element_size(),
+                                      n, F, A, float(C)))
+    return hv
+
+
+def linear_svc_linesearch_raw(dec, z, Y, t, workspace=None):
+    """sum over kept samples of max(0, 1 - y (dec + t z))^2 for step sizes t fp64 [T, A] (T <= 8) -> fp64 [T, A]; X is not read."""
+    lib = _abi.get_plugin()
+    _require_svc('linear_svc_linesearch', (dec, torch.float32, 'dec'), (z, torch.float32, 'z'), (Y, torch.int8, 'Y'), (t, torch.float64, 't'))
+    if dec.dim() != 2 or t.dim() != 2:
+        raise ValueError('linear_svc_linesearch: dec must be [n, A] and t [T, A]')
+    n, A = dec.shape
+    if tuple(z.shape) != (n, A) or tuple(Y.shape) != (n, A) or t.shape[1] != A:
+        raise ValueError('linear_svc_linesearch: shapes of dec, z, Y and t do not agree')
+    ws = linear_svc_workspace(n, 1, A, dec.device) if workspace is None else workspace
+    out = torch.empty_like(t)
+    _abi.check(lib.igan_linear_svc_linesearch(_stream(), _ptr(dec), _ptr(z), _ptr(Y), _ptr(t), _ptr(out), _ptr(ws), ws.numel() * ws.element_size(),
+                                              n, A, t.shape[0]))
+    return out
+
+
+def linear_svc_predict_raw(dec):
+    """pred int32 [n, A] = (dec > 0)."""
+    lib = _abi.get_plugin()
+    _require_svc('linear_svc_predict', (dec, torch.float32, 'dec'))
+    if dec.dim() != 2:
+        raise ValueError('linear_svc_predict: dec must be [n, A]')
+    pred = torch.empty(dec.shape, device=dec.device, dtype=torch.int32)
+    _abi.check(lib.igan_linear_svc_predict(_stream(), _ptr(dec), _ptr(pred), dec.shape[0], dec.shape[1]))
+    return pred
