@@ -40,7 +40,8 @@ extern "C" {
  * dy_pieces) belong to the bf16-piece form only; igan_conv2d_params gains x_colmax, igan_conv2d_wgrad_params x_colmax / dy_colmax at their ends;
  * 9: igan_conv2d_params gains w_pieces / w_pieces_bytes -- a caller-kept FILTER image for weights that never change (igan_filter_image_bytes, igan_filter_image);
  * 10: igan_knn_radius_update, igan_manifold_member_update; added under 10 without a bump, exports only: igan_ppl_endpoints, igan_ppl_crop_prep,
- * igan_linear_svc_workspace_bytes, igan_linear_svc_grad, igan_linear_svc_hv, igan_linear_svc_linesearch, igan_linear_svc_predict). */
+ * igan_linear_svc_workspace_bytes, igan_linear_svc_grad, igan_linear_svc_hv, igan_linear_svc_linesearch, igan_linear_svc_predict,
+ * igan_images_to_uint8, igan_images_from_uint8). */
 #define IGAN_ABI_VERSION 10
 
 typedef void* igan_stream_t; /* hipStream_t */
@@ -537,6 +538,34 @@ int igan_linear_svc_linesearch(igan_stream_t stream, const float* dec, const flo
                                const double* t /* [T][A] */, double* out /* [T][A] */, void* workspace, size_t workspace_bytes,
                                int n, int A, int T);
 int igan_linear_svc_predict(igan_stream_t stream, const float* dec, int* pred /* [n][A] */, int n, int A);
+
+/* ------------------------------------------------------------------------
+ * fp32 image batch <-> uint8 (reference: dnnlib/tflib/tfutil.py:245-267, convert_images_from_uint8 / convert_images_to_uint8:
+ * the output transform of every generator script and the conversion in front of every metric's feature network).  Added without a
+ * version bump: two more exports, no struct or signature changes.  Arguments are validated before anything touches a device.
+ *
+ * igan_images_to_uint8 replaces :255-267 (cast, avg_pool, transpose, scale + bias, saturate_cast) in one pass.  x is addressed
+ * through ELEMENT STRIDES, x[n][c][h][w] at n*stride_n + c*stride_c + h*stride_h + w*stride_w, so whatever layout G_synthesis hands
+ * back (a view with an offset included) is read in place.  y is contiguous bytes, [N][H/shrink][W/shrink][C] when nhwc, else
+ * [N][C][H/shrink][W/shrink]; the divisions floor, as VALID pooling does (a remainder of rows / columns is dropped).
+ *     m = (sum of the shrink x shrink box in fp32, rows then columns) * fp32(1 / shrink^2);   shrink == 1: m = x itself
+ *     v = m * scale + bias      the multiply and the add are two fp32 roundings, NEVER contracted into a fused multiply-add:
+ *                               values one ulp from (k - 128) / 127.5 -- where images that were uint8 once live -- give
+ *                               another byte under one rounding than under the reference's two
+ *     y = 0 for v < 0 or v == -inf;  255 for v >= 255 or v == +inf;  0 for NaN;  otherwise v truncated towards zero.
+ * The reference leaves NaN to an undefined cast (saturate_cast clamps, and a clamped NaN stays NaN); this kernel DEFINES it as 0.
+ * scale = 255 / (drange[1] - drange[0]) and bias = 0.5 - drange[0] * scale, computed by the caller in double and rounded once.
+ * Limits (IGAN_ERR_INVALID_ARGUMENT otherwise): non-null buffers, shrink >= 1, C >= 1, N, H, W >= 1, H / shrink and W / shrink >= 1,
+ * non-negative strides, N*C*H*W and the largest strided offset within int32.  C <= 4 are specialised; loads are 16-byte where
+ * stride_w == 1 (or the pixels are dense and channel-minor) and the addresses are 16-byte aligned, scalar otherwise.
+ *
+ * igan_images_from_uint8 replaces :245-252: x is [N][C][H][W] bytes, or [N][H][W][C] when nhwc_in; y is contiguous NCHW fp32,
+ *     y = float(x) * scale + bias       uncontracted; scale = (drange[1] - drange[0]) / 255, bias = drange[0]. */
+int igan_images_to_uint8(igan_stream_t stream, const float* x, unsigned char* y, int N, int C, int H, int W, int shrink,
+                         float scale, float bias, int nhwc,
+                         long long stride_n, long long stride_c, long long stride_h, long long stride_w);
+int igan_images_from_uint8(igan_stream_t stream, const unsigned char* x, float* y, int N, int C, int H, int W,
+                           float scale, float bias, int nhwc_in);
 
 /* ------------------------------------------------------------------------
  * Device-side time stamps (measurement support, not part of the reference's surface): igan_stamp writes the constant

@@ -19,6 +19,7 @@ finite-check are single streaming kernels (optimizer.py) instead of the referenc
 and one Adam chain per variable (dnnlib/tflib/optimizer.py:193-201,237-239).
 """
 import inspect
+import weakref
 from collections import OrderedDict
 
 import numpy as np
@@ -30,6 +31,25 @@ from . import tfutil
 from ... import hip_ops
 
 _ALIGN = 4  # floats (16 bytes)
+_LEGACY_OUTPUT_KWARGS = ('out_mul', 'out_add', 'out_shrink', 'out_dtype')     # network.py:527-560 of the reference: not built here
+_networks = weakref.WeakSet()       # live top-level networks (tflib.set_vars finds a variable's owner here)
+
+
+def find_var_owner(var_or_global_name):
+    """(top-level network, local name) of a variable given as the tensor itself or as '<network name>/<local name>'."""
+    nets = list(_networks)
+    if torch.is_tensor(var_or_global_name):
+        for net in nets:
+            for name, v in net.vars.items():
+                if v is var_or_global_name:
+                    return net, name
+        raise KeyError('set_vars: the tensor is not a variable of any live network')
+    name = str(var_or_global_name).split(':')[0]
+    for net in nets:
+        local = name[len(net.name) + 1:]
+        if name.startswith(net.name + '/') and local in net.vars:
+            return net, local
+    raise KeyError('set_vars: no live network has a variable %r' % name)
 
 
 def _resolve(func_name):
@@ -88,8 +108,10 @@ class Network:
         self.num_inputs = len(self.input_shapes)
         self.num_outputs = len(self.output_shapes)
 
+        self._run_staging = None          # run(): two pinned host buffers per output, kept between calls
         if parent is None:
             self._materialize()
+            _networks.add(self)
 
     # ------------------------------------------------------------------
     def _template_shape(self, arg_name):
@@ -365,26 +387,112 @@ class Network:
                             var.copy_(tfutil.lerp(src_net.vars[name], var, beta_nontrainable))
         return update_op
 
-    def run(self, *in_arrays, minibatch_size=None, num_gpus=1, return_as_list=False, **dynamic_kwargs):
-        """NumPy in, NumPy out, evaluated in minibatches without gradients (network.py:353-453)."""
+    def run(self, *in_arrays, input_transform=None, output_transform=None, return_as_list=False, print_progress=False,
+            minibatch_size=None, num_gpus=1, assume_frozen=False, **dynamic_kwargs):
+        """NumPy in, NumPy out, evaluated in minibatches without gradients (network.py:353-453).
+
+        in_arrays:          one array per network input; None stands for zeros of that input's shape (not all may be None).
+        input_transform:    dict(func=..., **kwargs): called on the device with the minibatch's input tensors as positional
+                            arguments before the network runs; returns a tensor or a list of tensors.  uint8 arrays reach
+                            it as uint8 (tflib.convert_images_from_uint8), everything else as float32.
+        output_transform:   the same for the output tensors, after the network (tflib.convert_images_to_uint8).  The returned
+                            arrays take the transformed dtype and shape.
+        return_as_list:     True = list of arrays; False = a single array, or a tuple for several outputs.
+        print_progress:     print 'done / total' while running.
+        minibatch_size:     maximum minibatch size, None = everything at once.
+        num_gpus, assume_frozen:    accepted for the reference's signature.  One process drives one GPU here and there is
+                            no graph to clone per GPU, so neither changes what runs.
+        dynamic_kwargs:     passed to the build function.  The reference's deprecated out_mul / out_add / out_shrink /
+                            out_dtype are not built: they raise a TypeError that points at output_transform.
+
+        Results leave the device through two pinned staging buffers per output on a copy stream of their own, an event
+        each: minibatch i is copied, and then gathered into the result by the host, while minibatch i + 1 computes.  The
+        buffers stay with the network between calls.  Without transforms the values are those of get_output_for bit for bit."""
+        legacy = [k for k in _LEGACY_OUTPUT_KWARGS if k in dynamic_kwargs]
+        if legacy:
+            raise TypeError('Network.run(): %s not supported; use output_transform=dict(func=tflib.convert_images_to_uint8, ...) instead'
+                            % ', '.join(legacy))
         assert len(in_arrays) == self.num_inputs
-        num_items = in_arrays[0].shape[0]
+        assert not all(arr is None for arr in in_arrays)
+        assert input_transform is None or callable(input_transform['func'])
+        assert output_transform is None or callable(output_transform['func'])
+        assert int(num_gpus) >= 1
+        num_items = next(arr for arr in in_arrays if arr is not None).shape[0]
         if minibatch_size is None:
             minibatch_size = num_items
+        minibatch_size = max(int(minibatch_size), 1)
+        staged = self.device.type == 'cuda'
         outs = None
+        pending = None      # (slot, begin, end, device tensors kept alive until their copy has finished)
+
+        def drain(job):
+            slot, begin, end, _keep = job
+            bufs, event = self._run_staging['slots'][slot]
+            event.synchronize()
+            for dst, buf in zip(outs, bufs):
+                dst[begin:end] = buf[:end - begin].numpy()
+
         with torch.no_grad():
-            for begin in range(0, num_items, minibatch_size):
+            for index, begin in enumerate(range(0, num_items, minibatch_size)):
+                if print_progress:
+                    print('\r%d / %d' % (begin, num_items), end='')
                 end = min(begin + minibatch_size, num_items)
-                ins = [torch.as_tensor(np.asarray(a[begin:end], dtype=np.float32)).to(self.device) for a in in_arrays]
+                ins = []
+                for arr, shape in zip(in_arrays, self.input_shapes):
+                    if arr is None:
+                        ins.append(torch.zeros([end - begin] + list(shape[1:]), dtype=torch.float32, device=self.device))
+                    else:
+                        keep = input_transform is not None and getattr(arr, 'dtype', None) == np.uint8
+                        ins.append(torch.as_tensor(np.asarray(arr[begin:end], dtype=np.uint8 if keep else np.float32)).to(self.device))
+                if input_transform is not None:
+                    kw = dict(input_transform)
+                    ins = kw.pop('func')(*ins, **kw)
+                    ins = [ins] if torch.is_tensor(ins) else list(ins)
+                assert len(ins) == self.num_inputs
                 mb = self.get_output_for(*ins, return_as_list=True, **dynamic_kwargs)
-                mb = [t.contiguous().cpu().numpy() for t in mb]
+                if output_transform is not None:
+                    kw = dict(output_transform)
+                    mb = kw.pop('func')(*mb, **kw)
+                    mb = [mb] if torch.is_tensor(mb) else list(mb)
+                assert len(mb) == self.num_outputs
+                live = [i for i, t in enumerate(mb) if t is not None]      # an output the build function switched off stays None
+                mb = [mb[i].contiguous() for i in live]
                 if outs is None:
-                    outs = [np.empty([num_items] + list(o.shape[1:]), dtype=o.dtype) for o in mb]
-                for dst, o in zip(outs, mb):
-                    dst[begin:end] = o
+                    outs = [np.empty([num_items] + list(t.shape[1:]), dtype=torch.empty(0, dtype=t.dtype).numpy().dtype) for t in mb]
+                if not staged:
+                    for dst, t in zip(outs, mb):
+                        dst[begin:end] = t.cpu().numpy()
+                    continue
+                slot = index & 1
+                bufs, event = self._staging_slot(slot, mb, min(minibatch_size, num_items))
+                stream = self._run_staging['stream']
+                stream.wait_stream(torch.cuda.current_stream(self.device))
+                with torch.cuda.stream(stream):
+                    for buf, t in zip(bufs, mb):
+                        buf[:end - begin].copy_(t, non_blocking=True)
+                    event.record(stream)
+                self._run_staging['uses'][slot] += 1
+                if pending is not None:
+                    drain(pending)          # the host gathers minibatch i - 1 while the device works on minibatch i
+                pending = (slot, begin, end, mb)
+            if pending is not None:
+                drain(pending)
+        if print_progress:
+            print('\r%d / %d' % (num_items, num_items))
+        outs = [outs[live.index(i)] if i in live else None for i in range(self.num_outputs)]
         if not return_as_list:
             outs = outs[0] if len(outs) == 1 else tuple(outs)
         return outs
+
+    def _staging_slot(self, slot, mb, capacity):
+        """The pinned buffers and the event of staging slot 0 / 1, (re)allocated when the outputs' geometry changes."""
+        key = tuple((tuple(t.shape[1:]), t.dtype) for t in mb)
+        st = self._run_staging
+        if st is None or st['key'] != key or st['capacity'] < capacity:
+            st = self._run_staging = dict(key=key, capacity=capacity, stream=torch.cuda.Stream(self.device), uses=[0, 0], slots=[
+                ([torch.empty((capacity,) + shape, dtype=dtype, pin_memory=True) for shape, dtype in key], torch.cuda.Event())
+                for _ in range(2)])
+        return st['slots'][slot]
 
     # ------------------------------------------------------------------
     # Pickle export / import in the layout of the reference's Network.__getstate__ / __setstate__ (network.py:255-299):

@@ -248,3 +248,46 @@ def random_uniform(shape, device, minval=0.0, maxval=1.0):
 
 def random_int(low, high, device):
     return _random.randint(low, high, device)
+
+#----------------------------------------------------------------------------
+# Inference transforms (tfutil.py:245-267) and set_vars (tfutil.py:211-232).
+
+def convert_images_from_uint8(images, drange=[-1,1], nhwc_to_nchw=False):
+    """Convert a minibatch of images from uint8 to float32 with configurable dynamic range.
+    Can be used as an input transformation for Network.run().  A ROCm tensor goes through one HIP kernel
+    (hip_ops.images_from_uint8); a CPU tensor takes the torch statement."""
+    images = torch.as_tensor(images)
+    if images.is_cuda and images.dtype == torch.uint8:
+        from ... import hip_ops
+        return hip_ops.images_from_uint8(images, drange, nhwc_to_nchw)
+    images = images.to(torch.float32)
+    if nhwc_to_nchw:
+        images = images.permute(0, 3, 1, 2)
+    return images * ((drange[1] - drange[0]) / 255) + drange[0]
+
+def convert_images_to_uint8(images, drange=[-1,1], nchw_to_nhwc=False, shrink=1):
+    """Convert a minibatch of images from float32 to uint8 with configurable dynamic range.
+    Can be used as an output transformation for Network.run().  A ROCm tensor goes through one HIP kernel
+    (hip_ops.images_to_uint8: pooling, range change, saturating cast and transpose in one pass, NaN -> 0); a CPU tensor
+    takes the torch statement (scale, + 0.5, clamp, truncating cast)."""
+    images = torch.as_tensor(images)
+    if images.is_cuda:
+        from ... import hip_ops
+        return hip_ops.images_to_uint8(images.to(torch.float32), drange, nchw_to_nhwc, shrink)
+    images = images.to(torch.float32)
+    if shrink > 1:
+        images = torch.nn.functional.avg_pool2d(images, shrink, shrink)
+    if nchw_to_nhwc:
+        images = images.permute(0, 2, 3, 1)
+    scale = 255 / (drange[1] - drange[0])
+    images = images * scale + (0.5 - drange[0] * scale)
+    return images.clamp(0, 255).to(torch.uint8)       # saturate_cast truncates after clamping
+
+def set_vars(var_to_value_dict):
+    """Set the values of given variables: {variable tensor or global name '<network name>/<local name>': value}.
+    A thin counterpart of tfutil.py:211-232 over Network.set_var, so that the owning network drops what it derived from
+    the old values."""
+    from . import network
+    for var, value in var_to_value_dict.items():
+        net, local = network.find_var_owner(var)
+        net.set_var(local, value)

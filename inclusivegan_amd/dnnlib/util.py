@@ -1,5 +1,6 @@
 """EasyDict / dotted-name helpers with the reference's contract (dnnlib/util.py:35-48,194-256)."""
 import importlib
+import os
 from typing import Any
 
 
@@ -63,3 +64,11 @@ def format_time(seconds) -> str:
     if total < 86400:
         return '%dh %02dm %02ds' % (hour, minute, sec)
     return '%dd %02dh %02dm' % (days, hour, minute)
+
+
+def next_run_dir(result_dir: str, run_desc: str) -> str:
+    """The run directory dnnlib.submit_run would create: <result_dir>/<next 5-digit id>-<run_desc>
+    (dnnlib/submission/submit.py:_create_run_dir_local).  Makes `result_dir`; the run directory itself is the caller's to make."""
+    os.makedirs(result_dir, exist_ok=True)
+    ids = [int(d.split('-')[0]) for d in os.listdir(result_dir) if d.split('-')[0].isdigit() and os.path.isdir(os.path.join(result_dir, d))]
+    return os.path.join(result_dir, '%05d-%s' % (max(ids) + 1 if ids else 0, run_desc))

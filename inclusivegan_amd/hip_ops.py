@@ -1961,6 +1961,67 @@ def ppl_crop_prep_raw(images, window, factor):
     return out
 
 
+# ---- fp32 images <-> uint8 (csrc/image_convert.hip; tfutil.convert_images_to_uint8 / convert_images_from_uint8) --------------
+def _drange(drange, name):
+    try:
+        lo, hi = (float(v) for v in drange)
+    except (TypeError, ValueError):
+        raise ValueError('%s: drange must be a pair of numbers (got %r)' % (name, drange))
+    if not (np.isfinite(lo) and np.isfinite(hi)) or lo == hi:
+        raise ValueError('%s: drange must be two different finite numbers (got %r)' % (name, drange))
+    return lo, hi
+
+
+def images_to_uint8(images, drange=(-1, 1), nchw_to_nhwc=False, shrink=1):
+    """tfutil.py:255-267 in one pass: images [N, C, H, W] fp32 in whatever strides they have -> contiguous uint8
+    [N, H // shrink, W // shrink, C] (nchw_to_nhwc) or [N, C, H // shrink, W // shrink].  scale and bias are the reference's
+    Python expressions evaluated in double and rounded to fp32 once.  An inference transform: no autograd."""
+    lib = _abi.get_plugin()
+    _require_cuda_f32(images)
+    if images.dim() != 4:
+        raise ValueError('images_to_uint8: images must be [N, C, H, W]')
+    lo, hi = _drange(drange, 'images_to_uint8')
+    shrink = int(shrink)
+    n, c, h, w = (int(v) for v in images.shape)
+    if shrink < 1 or h // shrink < 1 or w // shrink < 1:
+        raise ValueError('images_to_uint8: shrink must be between 1 and the smaller image side (got %d for %dx%d)' % (shrink, h, w))
+    if min(n, c) < 1:
+        raise ValueError('images_to_uint8: empty image batch %s' % (tuple(images.shape),))
+    scale = 255 / (hi - lo)
+    bias = 0.5 - lo * scale
+    images = images.detach()
+    oh, ow = h // shrink, w // shrink
+    out = torch.empty((n, oh, ow, c) if nchw_to_nhwc else (n, c, oh, ow), device=images.device, dtype=torch.uint8)
+    sn, sc, sh, sw = (int(v) for v in images.stride())
+    _abi.check(lib.igan_images_to_uint8(_stream(), _ptr(images), _ptr(out), n, c, h, w, shrink, float(np.float32(scale)), float(np.float32(bias)),
+                                        1 if nchw_to_nhwc else 0, sn, sc, sh, sw))
+    return out
+
+
+def images_from_uint8(images, drange=(-1, 1), nhwc_to_nchw=False):
+    """tfutil.py:245-252: uint8 [N, C, H, W] (or [N, H, W, C] with nhwc_to_nchw) -> contiguous fp32 [N, C, H, W],
+    float(x) * ((drange[1] - drange[0]) / 255) + drange[0].  No autograd."""
+    lib = _abi.get_plugin()
+    if not images.is_cuda:
+        raise RuntimeError('inclusivegan_amd kernels need tensors on a ROCm device (got %s); there is no CPU path' % images.device)
+    if images.dtype != torch.uint8:
+        raise TypeError('images_from_uint8: images must be uint8 (got %s)' % images.dtype)
+    if images.dim() != 4:
+        raise ValueError('images_from_uint8: images must have four dimensions')
+    if images.numel() == 0:
+        raise ValueError('images_from_uint8: empty image batch %s' % (tuple(images.shape),))
+    lo, hi = _drange(drange, 'images_from_uint8')
+    images = images.contiguous()
+    if nhwc_to_nchw:
+        n, h, w, c = (int(v) for v in images.shape)
+    else:
+        n, c, h, w = (int(v) for v in images.shape)
+    out = torch.empty((n, c, h, w), device=images.device, dtype=torch.float32)
+    _abi.check(lib.igan_images_from_uint8(_stream(), _ptr(images), _ptr(out), n, c, h, w, float(np.float32((hi - lo) / 255)), float(np.float32(lo)),
+                                          1 if nhwc_to_nchw else 0))
+    return out
+
+
 # ----------------------------------------------------------------------------
 # optimizer
 

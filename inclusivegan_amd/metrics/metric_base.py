@@ -18,15 +18,9 @@ from ..dnnlib.tflib import tfutil
 
 
 def convert_images_to_uint8(images, drange=[-1, 1], nchw_to_nhwc=False, shrink=1):
-    """float images -> uint8 with the reference's rounding (dnnlib/tflib/tfutil.py:255-267: scale, + 0.5, saturating cast)."""
-    images = images.to(torch.float32)
-    if shrink > 1:
-        images = torch.nn.functional.avg_pool2d(images, shrink, shrink)
-    if nchw_to_nhwc:
-        images = images.permute(0, 2, 3, 1)
-    scale = 255 / (drange[1] - drange[0])
-    images = images * scale + (0.5 - drange[0] * scale)
-    return images.clamp(0, 255).to(torch.uint8)       # saturate_cast truncates after clamping
+    """float images -> uint8 with the reference's rounding (dnnlib/tflib/tfutil.py:255-267: scale, + 0.5, saturating cast):
+    tflib.convert_images_to_uint8 -- one HIP kernel for a device tensor, the torch statement for a CPU tensor."""
+    return tfutil.convert_images_to_uint8(images, drange=drange, nchw_to_nhwc=nchw_to_nhwc, shrink=shrink)
 
 
 class _Result:

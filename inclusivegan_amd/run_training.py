@@ -15,6 +15,7 @@ import os
 import sys
 
 from .dnnlib import EasyDict
+from .dnnlib.util import next_run_dir
 
 _CONFIGS_E = ['config-e-G%s-D%s' % (g, d) for g in ('orig', 'resnet', 'skip') for d in ('orig', 'resnet', 'skip')]
 _valid_configs = ['config-a', 'config-b', 'config-c', 'config-d', 'config-e', 'config-f'] + _CONFIGS_E
@@ -91,9 +92,7 @@ def run(attr_file=None, **args):
     # the run directory dnnlib.submit_run would create: <result_dir>/<next 5-digit id>-<run_desc> (dnnlib/submission/submit.py:_create_run_dir_local)
     result_dir = args.get('result_dir')
     if result_dir is not None and int(os.environ.get('RANK', '0')) == 0:
-        os.makedirs(result_dir, exist_ok=True)
-        ids = [int(d.split('-')[0]) for d in os.listdir(result_dir) if d.split('-')[0].isdigit() and os.path.isdir(os.path.join(result_dir, d))]
-        kw['run_dir'] = os.path.join(result_dir, '%05d-%s' % (max(ids) + 1 if ids else 0, run_desc))
+        kw['run_dir'] = next_run_dir(result_dir, run_desc)
     # synthetic data source (no tfrecords reader in this round): shape follows the dataset name
     ds = kw['dataset_args']
     if 'mnist' in ds['tfrecord_dir']:
