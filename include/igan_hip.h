@@ -41,7 +41,8 @@ extern "C" {
  * 9: igan_conv2d_params gains w_pieces / w_pieces_bytes -- a caller-kept FILTER image for weights that never change (igan_filter_image_bytes, igan_filter_image);
  * 10: igan_knn_radius_update, igan_manifold_member_update; added under 10 without a bump, exports only: igan_ppl_endpoints, igan_ppl_crop_prep,
  * igan_linear_svc_workspace_bytes, igan_linear_svc_grad, igan_linear_svc_hv, igan_linear_svc_linesearch, igan_linear_svc_predict,
- * igan_images_to_uint8, igan_images_from_uint8). */
+ * igan_images_to_uint8, igan_images_from_uint8, igan_dense_small2_grouped, igan_dense_small_wgrad2_grouped, igan_rows_group_sum,
+ * igan_scale_add). */
 #define IGAN_ABI_VERSION 10
 
 typedef void* igan_stream_t; /* hipStream_t */
@@ -55,7 +56,7 @@ enum igan_status {
 
 int igan_abi_version(void);
 /* sizeof() of the parameter structs as this library was compiled, by id: 0 upfirdn2d, 1 fused_bias_act, 2 conv2d,
- * 3 conv2d_wgrad, 4 dense, 5 dense_wgrad, 6 taps; 0 for an unknown id.  A binding checks these against its own
+ * 3 conv2d_wgrad, 4 dense, 5 dense_wgrad, 6 taps, 7 dense2, 8 dense_wgrad2; 0 for an unknown id.  A binding checks these against its own
  * struct declarations at load time, so that a stale library can never be driven with a newer struct (or vice versa). */
 size_t igan_struct_size(int which);
 const char* igan_last_error(void);
@@ -360,6 +361,46 @@ int igan_dense_small_wgrad(igan_stream_t stream, const igan_dense_wgrad_params* 
 int igan_dense_small_grouped(igan_stream_t stream, const igan_dense_params* groups, int count);
 int igan_dense_small_wgrad_grouped(igan_stream_t stream, const igan_dense_wgrad_params* groups, int count);
 
+/* The style path differentiated twice (path-length regulariser, training/loss.py:60-66), closed: with e = -c^2/2 gd d^3,
+ * m = e . wsq^T, sigma = gs + 2 s m, the latent gradient dy = c_a sigma . A^T is a differentiable op whose own backward is
+ * written out (hip_ops.StyleGradAllFn).  What its lines need beyond igan_dense_params:
+ *     prologue MUL          pro_scale * x * x2                                    (r = 2 v s)
+ *     y2 != NULL            with the epilogues above: y2[m,n] = alpha * sum, the product itself beside its epilogue form
+ *     epilogue DEMOD_GRAD2  y = -1/2 v e2^3,  y2 = 3/4 v e1 e2^5                  (gd_bar and q_bar from v = c^2 e_bar; e1 = gd, e2 = d)
+ *     epilogue STYLE_GRAD2  y = 2 (e2 v + e1 e3)  [+ colsum as STYLE_GRAD]        (s_bar; e2 = s, e1 = v, e3 = m)
+ * and a two-term weight-gradient form
+ *     dw[k,n] = alpha * sum_m a[m,k] a2[m,k] pro_b(b)[m,n] + alpha2 * sum_m pro_c(c)[m,k] d[m,n]
+ * (a2 NULL = 1; c NULL = no second term; pro_b NONE|DEMOD_GRAD with b2, pro_c NONE|SQUARE).  e3 / y2 / a2 / d are contiguous [M, N] / [M, K].
+ * igan_struct_size ids 7 and 8. */
+enum { IGAN_DENSE_PRO_MUL = 3 };
+enum { IGAN_DENSE_EPI_DEMOD_GRAD2 = 4, IGAN_DENSE_EPI_STYLE_GRAD2 = 5 };
+typedef struct igan_dense2_params {
+    igan_dense_params p;
+    const float* e3;
+    float* y2;
+} igan_dense2_params;
+int igan_dense_small2_grouped(igan_stream_t stream, const igan_dense2_params* groups, int count);
+
+typedef struct igan_dense_wgrad2_params {
+    const float* a;         /* [M, K], row stride lda floats */
+    const float* a2;        /* [M, K] contiguous or NULL */
+    const float* b;         /* [M, N] contiguous */
+    const float* b2;        /* DEMOD_GRAD: [M, N] contiguous, else NULL */
+    const float* c;         /* [M, K], row stride ldc floats, or NULL */
+    const float* d;         /* [M, N] contiguous (with c) */
+    float* dw;              /* [K, N] */
+    int lda, ldc;
+    int M, K, N;
+    int pro_b, pro_c;
+    float alpha, pro_scale, alpha2;
+} igan_dense_wgrad2_params;
+int igan_dense_small_wgrad2_grouped(igan_stream_t stream, const igan_dense_wgrad2_params* groups, int count);
+
+/* out[m, j, :] = sum over the groups l with slot[l] == j, in order, of src[l, m, :]  (zero where no group names j): the per-layer
+ * latent gradients [count, M, D] of one synthesis pass gathered into the gradient of the latents [M, L, D].  `slot` is a HOST
+ * pointer (count <= IGAN_DENSE_MAX_GROUPS entries).  D % 4 == 0; deterministic. */
+int igan_rows_group_sum(igan_stream_t stream, const float* src, const int* slot, int count, float* out, int M, int L, int D);
+
 /* out[i] = sum_t w[t*n + i]^2  (sum over the filter taps of the squared weights: the [Cin,Cout] matrix of the
  * demodulation, :105) and out[t*n + i] = scale * w[t*n + i] * v[i] (its gradient back onto the filter). */
 int igan_sumsq_taps(igan_stream_t stream, const float* w, float* out, int taps, int n);
@@ -383,6 +424,12 @@ int igan_bcast_mul_taps_grouped(igan_stream_t stream, const igan_taps_params* gr
 size_t igan_scale_dot_workspace_floats(int N, int HW, int C);
 int igan_scale_dot(igan_stream_t stream, const float* a, const float* b, const float* s, float* out,
                    float* dot, float* workspace, int N, int HW, int C);
+
+/* out[n,hw,c] = a[n,hw,c] * alpha[n,c] + b[n,hw,c] * beta[n,c] on channel-minor tensors (C % 4 == 0): the element-wise lines of the
+ * modulated convolution's second-order backward in one pass.  Either term may be absent (a or b NULL); alpha / beta NULL = 1;
+ * out may alias a (every element is read before it is written, by the lane that writes it), not b. */
+int igan_scale_add(igan_stream_t stream, const float* a, const float* alpha, const float* b, const float* beta, float* out,
+                   int N, int HW, int C);
 
 /* LPIPS per-layer distance (Zhang et al. 2018; role of lpips.get_output_for, training/loss.py:31,41) on raw
  * channel-minor VGG features fa, fb [N, HW, C], C in {64,128,256,512}, lin[C] >= 0:

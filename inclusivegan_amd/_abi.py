@@ -117,12 +117,30 @@ class TapsParams(ctypes.Structure):
                 ('taps', ctypes.c_int), ('n', ctypes.c_int), ('scale', ctypes.c_float)]
 
 
+class Dense2Params(ctypes.Structure):
+    _fields_ = [('p', DenseParams), ('e3', ctypes.c_void_p), ('y2', ctypes.c_void_p)]
+
+
+class DenseWgrad2Params(ctypes.Structure):
+    _fields_ = [
+        ('a', ctypes.c_void_p), ('a2', ctypes.c_void_p), ('b', ctypes.c_void_p), ('b2', ctypes.c_void_p),
+        ('c', ctypes.c_void_p), ('d', ctypes.c_void_p), ('dw', ctypes.c_void_p),
+        ('lda', ctypes.c_int), ('ldc', ctypes.c_int),
+        ('M', ctypes.c_int), ('K', ctypes.c_int), ('N', ctypes.c_int),
+        ('pro_b', ctypes.c_int), ('pro_c', ctypes.c_int),
+        ('alpha', ctypes.c_float), ('pro_scale', ctypes.c_float), ('alpha2', ctypes.c_float),
+    ]
+
+
 ABI_VERSION = 10     # include/igan_hip.h IGAN_ABI_VERSION
-STRUCTS = (UpFirDn2DParams, FusedBiasActParams, Conv2DParams, Conv2DWgradParams, DenseParams, DenseWgradParams, TapsParams)   # igan_struct_size ids
+STRUCTS = (UpFirDn2DParams, FusedBiasActParams, Conv2DParams, Conv2DWgradParams, DenseParams, DenseWgradParams, TapsParams,
+           Dense2Params, DenseWgrad2Params)   # igan_struct_size ids
 
 DENSE_MAX_GROUPS = 24
 DENSE_PRO_NONE, DENSE_PRO_SQUARE, DENSE_PRO_DEMOD_GRAD = 0, 1, 2
 DENSE_EPI_SCALE, DENSE_EPI_BIAS, DENSE_EPI_RSQRT, DENSE_EPI_STYLE_GRAD = 0, 1, 2, 3
+DENSE_PRO_MUL = 3                                                      # second-order style path (igan_dense_small2_grouped)
+DENSE_EPI_DEMOD_GRAD2, DENSE_EPI_STYLE_GRAD2 = 4, 5
 
 _I, _F, _P, _SZ, _LL = ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_longlong
 
@@ -162,6 +180,10 @@ SIGNATURES = {
     'igan_dense_small_wgrad': (_I, [_P, ctypes.POINTER(DenseWgradParams)]),
     'igan_dense_small_grouped': (_I, [_P, ctypes.POINTER(DenseParams), _I]),
     'igan_dense_small_wgrad_grouped': (_I, [_P, ctypes.POINTER(DenseWgradParams), _I]),
+    'igan_dense_small2_grouped': (_I, [_P, ctypes.POINTER(Dense2Params), _I]),
+    'igan_dense_small_wgrad2_grouped': (_I, [_P, ctypes.POINTER(DenseWgrad2Params), _I]),
+    'igan_rows_group_sum': (_I, [_P, _P, ctypes.POINTER(ctypes.c_int), _I, _P, _I, _I, _I]),
+    'igan_scale_add': (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I]),
     'igan_sumsq_taps_grouped': (_I, [_P, ctypes.POINTER(TapsParams), _I]),
     'igan_bcast_mul_taps_grouped': (_I, [_P, ctypes.POINTER(TapsParams), _I]),
     'igan_sumsq_taps': (_I, [_P, _P, _P, _I, _I]),

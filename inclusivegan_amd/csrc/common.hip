@@ -29,6 +29,8 @@ extern "C" size_t igan_struct_size(int which) {
         case 4: return sizeof(igan_dense_params);
         case 5: return sizeof(igan_dense_wgrad_params);
         case 6: return sizeof(igan_taps_params);
+        case 7: return sizeof(igan_dense2_params);
+        case 8: return sizeof(igan_dense_wgrad2_params);
         default: return 0;
     }
 }

@@ -31,6 +31,7 @@ __host__ __device__ constexpr int ds_ks(int MB) { return MB > 32 ? 256 : 512; }
 __device__ __forceinline__ float pro_apply(int pro, float v, float v2, float ps) {
     if (pro == IGAN_DENSE_PRO_SQUARE) return v * v;
     if (pro == IGAN_DENSE_PRO_DEMOD_GRAD) return ps * v * v2 * v2 * v2;    // -1/2 c^2 dd d^3 with ps = -c^2/2
+    if (pro == IGAN_DENSE_PRO_MUL) return ps * v * v2;                     // r = 2 v s of the second-order style path
     return v;
 }
 
@@ -39,13 +40,17 @@ __device__ __forceinline__ float pro_apply(int pro, float v, float v2, float ps)
 // the chain is  [one round of loads] -> [LDS image of x] -> [FMAs] -> [group reduce].
 // Up to IGAN_DENSE_MAX_GROUPS independent problems per launch (blockIdx.y): the 18 style affines / 12 demodulations
 // of one generator pass are one launch instead of 30.
-struct DenseGroups { igan_dense_params g[IGAN_DENSE_MAX_GROUPS]; };
+struct DenseGroups { igan_dense2_params g[IGAN_DENSE_MAX_GROUPS]; };      // the plain entry points leave e3 / y2 NULL
 struct WgradGroups { igan_dense_wgrad_params g[IGAN_DENSE_MAX_GROUPS]; };
+struct Wgrad2Groups { igan_dense_wgrad2_params g[IGAN_DENSE_MAX_GROUPS]; };
+struct RowsSumArgs { int slot[IGAN_DENSE_MAX_GROUPS]; };
 struct TapsGroups { igan_taps_params g[IGAN_DENSE_MAX_GROUPS]; };
 
 template <int MB, bool WT>
 __global__ __launch_bounds__(256) void dense_small_kernel(DenseGroups G) {
-    const igan_dense_params a = G.g[blockIdx.y];
+    const igan_dense_params a = G.g[blockIdx.y].p;
+    const float* __restrict__ e3 = G.g[blockIdx.y].e3;
+    float* __restrict__ y2 = G.g[blockIdx.y].y2;
     if ((int)blockIdx.x * DS_COLS >= a.N) return;      // groups differ in width (uniform per workgroup)
     constexpr int DS_KS = ds_ks(MB);
     constexpr int DS_NIT = DS_KS / (4 * DS_GROUPS);   // float4 k-groups per lane per super-tile
@@ -110,7 +115,7 @@ __global__ __launch_bounds__(256) void dense_small_kernel(DenseGroups G) {
             const int k = k0 + 4 * kv;
             const bool ok = (m < M) && (k < K);
             xv[q] = ld4(rx, ok ? ((unsigned)m * (unsigned)a.ldx + (unsigned)k) * 4u : OOB);
-            xu[q] = ld4(rx2, (ok && a.prologue == IGAN_DENSE_PRO_DEMOD_GRAD) ? ((unsigned)m * (unsigned)K + (unsigned)k) * 4u : OOB);
+            xu[q] = ld4(rx2, (ok && a.prologue >= IGAN_DENSE_PRO_DEMOD_GRAD) ? ((unsigned)m * (unsigned)K + (unsigned)k) * 4u : OOB);
         }
         if (k0 > 0) __syncthreads();         // the previous super-tile's readers are done with xs
 #pragma unroll
@@ -148,11 +153,18 @@ __global__ __launch_bounds__(256) void dense_small_kernel(DenseGroups G) {
         float v = 0.f;
         if (m < M && jj < N) {
             v = s * a.alpha;
+            if (y2 && a.epilogue != IGAN_DENSE_EPI_DEMOD_GRAD2) y2[(size_t)m * N + jj] = v;      // the product itself, beside its epilogue form (m of the style gradient)
             if (a.epilogue == IGAN_DENSE_EPI_BIAS) v += a.bias_scale * a.bias[jj] + a.add_const;
             else if (a.epilogue == IGAN_DENSE_EPI_RSQRT) v = rsqrtf(v + a.eps);
             else if (a.epilogue == IGAN_DENSE_EPI_STYLE_GRAD) {
                 v = 2.0f * a.e2[(size_t)m * N + jj] * v;
                 if (a.e1) v += a.e1[(size_t)m * N + jj];
+            } else if (a.epilogue == IGAN_DENSE_EPI_DEMOD_GRAD2) {      // v = c^2 e_bar:  y = gd_bar = -1/2 v d^3,  y2 = q_bar = 3/4 v gd d^5   (e1 = gd, e2 = d)
+                const float dd = a.e2[(size_t)m * N + jj], d3 = dd * dd * dd;
+                y2[(size_t)m * N + jj] = 0.75f * v * a.e1[(size_t)m * N + jj] * d3 * dd * dd;
+                v = -0.5f * v * d3;
+            } else if (a.epilogue == IGAN_DENSE_EPI_STYLE_GRAD2) {      // s_bar = 2 (s v + e1 e3)   (e2 = s, e1 = v of the latent cotangent, e3 = m)
+                v = 2.0f * fmaf(a.e2[(size_t)m * N + jj], v, a.e1[(size_t)m * N + jj] * e3[(size_t)m * N + jj]);
             }
             a.y[(size_t)m * a.ldy + jj] = v;
         }
@@ -205,6 +217,69 @@ __global__ __launch_bounds__(256) void dense_small_wgrad_kernel(WgradGroups G) {
         make_float4(acc.x * p.alpha, acc.y * p.alpha, acc.z * p.alpha, acc.w * p.alpha);
 }
 
+// Two-term form for the second-order style path:  dw[k][n] = alpha * sum_m a a2 pro_b(b) + alpha2 * sum_m pro_c(c) d
+// (W2_bar = r^T e + c^2 (s s)^T q_bar,  A_bar = c_a (g^T sigma + y^T s_bar)); the terms are summed apart, rows in order.
+__global__ __launch_bounds__(256) void dense_small_wgrad2_kernel(Wgrad2Groups G) {
+    const igan_dense_wgrad2_params p = G.g[blockIdx.y];
+    const int nv = p.N >> 2;
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= p.K * nv) return;
+    const int k = idx / nv, n4 = idx - k * nv;
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f), acc2 = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int m0 = 0; m0 < p.M; m0 += 8) {
+        float xv[8], cv[8];
+        float4 b[8], u[8], d[8];
+#pragma unroll
+        for (int q = 0; q < 8; q++) {
+            const int m = min(m0 + q, p.M - 1);      // clamped: always a valid address, masked below
+            xv[q] = p.a[(size_t)m * p.lda + k];
+            if (p.a2) xv[q] *= p.a2[(size_t)m * p.K + k];
+            b[q] = *reinterpret_cast<const float4*>(p.b + (size_t)m * p.N + 4 * n4);
+            if (p.pro_b == IGAN_DENSE_PRO_DEMOD_GRAD) u[q] = *reinterpret_cast<const float4*>(p.b2 + (size_t)m * p.N + 4 * n4);
+            if (p.c) {
+                cv[q] = p.c[(size_t)m * p.ldc + k];
+                d[q] = *reinterpret_cast<const float4*>(p.d + (size_t)m * p.N + 4 * n4);
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < 8; q++) {
+            const bool live = m0 + q < p.M;
+            const float x = live ? xv[q] : 0.f;
+            float4 t = b[q];
+            if (p.pro_b == IGAN_DENSE_PRO_DEMOD_GRAD) {
+                t.x = p.pro_scale * t.x * u[q].x * u[q].x * u[q].x; t.y = p.pro_scale * t.y * u[q].y * u[q].y * u[q].y;
+                t.z = p.pro_scale * t.z * u[q].z * u[q].z * u[q].z; t.w = p.pro_scale * t.w * u[q].w * u[q].w * u[q].w;
+            }
+            acc.x = fmaf(x, t.x, acc.x); acc.y = fmaf(x, t.y, acc.y);
+            acc.z = fmaf(x, t.z, acc.z); acc.w = fmaf(x, t.w, acc.w);
+            if (p.c) {
+                float c = live ? cv[q] : 0.f;
+                if (p.pro_c == IGAN_DENSE_PRO_SQUARE) c *= c;
+                acc2.x = fmaf(c, d[q].x, acc2.x); acc2.y = fmaf(c, d[q].y, acc2.y);
+                acc2.z = fmaf(c, d[q].z, acc2.z); acc2.w = fmaf(c, d[q].w, acc2.w);
+            }
+        }
+    }
+    *reinterpret_cast<float4*>(p.dw + (size_t)k * p.N + 4 * n4) =
+        make_float4(acc.x * p.alpha + acc2.x * p.alpha2, acc.y * p.alpha + acc2.y * p.alpha2,
+                    acc.z * p.alpha + acc2.z * p.alpha2, acc.w * p.alpha + acc2.w * p.alpha2);
+}
+
+// out[m][j][:] = sum over the groups l with slot[l] == j, in order, of src[l][m][:]  (zero where a slot has none): the per-layer
+// latent gradients of one synthesis pass gathered into the gradient of the [M, L, D] latents.
+__global__ __launch_bounds__(256) void rows_group_sum_kernel(const float* __restrict__ src, float* __restrict__ out, RowsSumArgs A, int count, int M, int L, int D4) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= M * L * D4) return;
+    const int c = i % D4, j = (i / D4) % L, m = i / (D4 * L);
+    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int l = 0; l < count; l++) {
+        if (A.slot[l] != j) continue;
+        const float4 v = reinterpret_cast<const float4*>(src)[((size_t)l * M + m) * D4 + c];
+        s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
+    }
+    reinterpret_cast<float4*>(out)[i] = s;
+}
+
 // out[i] = sum_t w[t][i]^2
 __global__ __launch_bounds__(256) void sumsq_taps_kernel(TapsGroups G) {
     const igan_taps_params q = G.g[blockIdx.y];
@@ -245,16 +320,18 @@ void launch_dense(hipStream_t stream, const DenseGroups& G, int count, int maxN,
     else hipLaunchKernelGGL((dense_small_kernel<MB, false>), grid, dim3(256), 0, stream, G);
 }
 
-int dense_check(const igan_dense_params* p) {
+int dense_check(const igan_dense_params* p, const float* e3 = nullptr, const float* y2 = nullptr, bool second = false) {
     IGAN_REQUIRE(p->x && p->w && p->y, "dense_small: null buffer");
     IGAN_REQUIRE(p->M >= 1 && p->M <= IGAN_DENSE_MAX_ROWS, "dense_small: 1 <= M <= %d rows (use igan_conv2d for larger batches)", IGAN_DENSE_MAX_ROWS);
     IGAN_REQUIRE(p->K >= 4 && p->K % 4 == 0 && p->N >= 1, "dense_small: K must be a positive multiple of 4, N positive");
     IGAN_REQUIRE(p->ldx >= p->K && p->ldx % 4 == 0 && p->ldy >= p->N, "dense_small: bad row strides");
     IGAN_REQUIRE(igan::dense_small_fits(p->M, p->K, p->N, p->ldx), "dense_small: x, x2 and w must each stay below 2 GiB (32-bit buffer offsets; use igan_conv2d for larger operands)");
     IGAN_REQUIRE((((uintptr_t)p->x) & 15) == 0 && (!p->w_transposed || (((uintptr_t)p->w) & 15) == 0), "dense_small: x (and a transposed w) must be 16-byte aligned");
-    IGAN_REQUIRE(p->prologue >= IGAN_DENSE_PRO_NONE && p->prologue <= IGAN_DENSE_PRO_DEMOD_GRAD, "dense_small: unknown prologue");
-    IGAN_REQUIRE(p->epilogue >= IGAN_DENSE_EPI_SCALE && p->epilogue <= IGAN_DENSE_EPI_STYLE_GRAD, "dense_small: unknown epilogue");
-    IGAN_REQUIRE(p->prologue != IGAN_DENSE_PRO_DEMOD_GRAD || (p->x2 && (((uintptr_t)p->x2) & 15) == 0), "dense_small: demod-gradient prologue needs an aligned x2");
+    IGAN_REQUIRE(p->prologue >= IGAN_DENSE_PRO_NONE && p->prologue <= (second ? IGAN_DENSE_PRO_MUL : IGAN_DENSE_PRO_DEMOD_GRAD), "dense_small: unknown prologue");
+    IGAN_REQUIRE(p->epilogue >= IGAN_DENSE_EPI_SCALE && p->epilogue <= (second ? IGAN_DENSE_EPI_STYLE_GRAD2 : IGAN_DENSE_EPI_STYLE_GRAD), "dense_small: unknown epilogue");
+    IGAN_REQUIRE(p->prologue < IGAN_DENSE_PRO_DEMOD_GRAD || (p->x2 && (((uintptr_t)p->x2) & 15) == 0), "dense_small: a two-operand prologue needs an aligned x2");
+    IGAN_REQUIRE(p->epilogue != IGAN_DENSE_EPI_DEMOD_GRAD2 || (p->e1 && p->e2 && y2), "dense_small: the second-order demodulation epilogue needs e1, e2 and y2");
+    IGAN_REQUIRE(p->epilogue != IGAN_DENSE_EPI_STYLE_GRAD2 || (p->e1 && p->e2 && e3), "dense_small: the second-order style epilogue needs e1, e2 and e3");
     IGAN_REQUIRE(p->epilogue != IGAN_DENSE_EPI_BIAS || p->bias, "dense_small: bias epilogue needs a bias");
     IGAN_REQUIRE(p->epilogue != IGAN_DENSE_EPI_STYLE_GRAD || p->e2, "dense_small: style-gradient epilogue needs e2");
     return IGAN_OK;
@@ -268,6 +345,17 @@ int wgrad_check(const igan_dense_wgrad_params* p) {
     IGAN_REQUIRE(p->pro_a == IGAN_DENSE_PRO_NONE || p->pro_a == IGAN_DENSE_PRO_SQUARE, "dense_small_wgrad: unknown prologue for a");
     IGAN_REQUIRE(p->pro_b == IGAN_DENSE_PRO_NONE || (p->pro_b == IGAN_DENSE_PRO_DEMOD_GRAD && p->b2 && (((uintptr_t)p->b2) & 15) == 0), "dense_small_wgrad: bad prologue for b");
     IGAN_REQUIRE((long long)p->K * p->N <= INT32_MAX, "dense_small_wgrad: too large");
+    return IGAN_OK;
+}
+
+int wgrad2_check(const igan_dense_wgrad2_params* p) {
+    IGAN_REQUIRE(p->a && p->b && p->dw && (!p->c || p->d), "dense_small_wgrad2: null buffer");
+    IGAN_REQUIRE(p->M >= 1 && p->M <= IGAN_DENSE_MAX_ROWS, "dense_small_wgrad2: 1 <= M <= %d rows", IGAN_DENSE_MAX_ROWS);
+    IGAN_REQUIRE(p->K >= 1 && p->N >= 4 && p->N % 4 == 0 && p->lda >= p->K && (!p->c || p->ldc >= p->K), "dense_small_wgrad2: N must be a positive multiple of 4");
+    IGAN_REQUIRE(((((uintptr_t)p->b) | ((uintptr_t)p->d) | ((uintptr_t)p->dw)) & 15) == 0, "dense_small_wgrad2: b, d and dw must be 16-byte aligned");
+    IGAN_REQUIRE(p->pro_c == IGAN_DENSE_PRO_NONE || p->pro_c == IGAN_DENSE_PRO_SQUARE, "dense_small_wgrad2: unknown prologue for c");
+    IGAN_REQUIRE(p->pro_b == IGAN_DENSE_PRO_NONE || (p->pro_b == IGAN_DENSE_PRO_DEMOD_GRAD && p->b2 && (((uintptr_t)p->b2) & 15) == 0), "dense_small_wgrad2: bad prologue for b");
+    IGAN_REQUIRE((long long)p->K * p->N <= INT32_MAX, "dense_small_wgrad2: too large");
     return IGAN_OK;
 }
 
@@ -301,18 +389,23 @@ bool dense_small_ok(int M, int K, int N, const void* x, const void* w, bool wt) 
 int dense_small_rows(int M) { return M <= 8 ? 8 : (M <= 16 ? 16 : (M <= 24 ? 24 : (M <= 32 ? 32 : (M <= 48 ? 48 : 64)))); }
 
 // all groups of one launch share the weight layout (w_transposed) and the row-count bucket
-void dense_small_launch_groups(hipStream_t stream, const igan_dense_params* groups, int count) {
-    DenseGroups G;
+static void dense_small_launch_filled(hipStream_t stream, const DenseGroups& G, int count) {
     int maxM = 1, maxN = 1;
-    for (int i = 0; i < count; i++) { G.g[i] = groups[i]; maxM = std::max(maxM, groups[i].M); maxN = std::max(maxN, groups[i].N); }
+    for (int i = 0; i < count; i++) { maxM = std::max(maxM, G.g[i].p.M); maxN = std::max(maxN, G.g[i].p.N); }
     const int mb = dense_small_rows(maxM);
-    const bool wt = groups[0].w_transposed != 0;
+    const bool wt = G.g[0].p.w_transposed != 0;
     if (mb == 8) launch_dense<8>(stream, G, count, maxN, wt);
     else if (mb == 16) launch_dense<16>(stream, G, count, maxN, wt);
     else if (mb == 24) launch_dense<24>(stream, G, count, maxN, wt);
     else if (mb == 32) launch_dense<32>(stream, G, count, maxN, wt);
     else if (mb == 48) launch_dense<48>(stream, G, count, maxN, wt);
     else launch_dense<64>(stream, G, count, maxN, wt);
+}
+
+void dense_small_launch_groups(hipStream_t stream, const igan_dense_params* groups, int count) {
+    DenseGroups G;
+    for (int i = 0; i < count; i++) { G.g[i].p = groups[i]; G.g[i].e3 = nullptr; G.g[i].y2 = nullptr; }
+    dense_small_launch_filled(stream, G, count);
 }
 
 void dense_small_launch(hipStream_t stream, const igan_dense_params& a) { dense_small_launch_groups(stream, &a, 1); }
@@ -407,4 +500,46 @@ extern "C" int igan_sumsq_taps_grouped(igan_stream_t stream_, const igan_taps_pa
 
 extern "C" int igan_bcast_mul_taps_grouped(igan_stream_t stream_, const igan_taps_params* groups, int count) {
     return taps_launch(stream_, groups, count, true, "bcast_mul_taps");
+}
+
+extern "C" int igan_dense_small2_grouped(igan_stream_t stream_, const igan_dense2_params* groups, int count) {
+    using namespace igan;
+    IGAN_REQUIRE(groups && count >= 1 && count <= IGAN_DENSE_MAX_GROUPS, "dense_small2: 1 <= count <= %d groups", IGAN_DENSE_MAX_GROUPS);
+    DenseGroups G;
+    for (int i = 0; i < count; i++) {
+        if (int rc = dense_check(&groups[i].p, groups[i].e3, groups[i].y2, true)) return rc;
+        IGAN_REQUIRE((groups[i].p.w_transposed != 0) == (groups[0].p.w_transposed != 0), "dense_small2: the groups of one launch share w_transposed");
+        G.g[i] = groups[i];
+    }
+    dense_small_launch_filled((hipStream_t)stream_, G, count);
+    IGAN_LAUNCH_CHECK("dense_small2 launch");
+    return IGAN_OK;
+}
+
+extern "C" int igan_dense_small_wgrad2_grouped(igan_stream_t stream_, const igan_dense_wgrad2_params* groups, int count) {
+    using namespace igan;
+    IGAN_REQUIRE(groups && count >= 1 && count <= IGAN_DENSE_MAX_GROUPS, "dense_small_wgrad2: 1 <= count <= %d groups", IGAN_DENSE_MAX_GROUPS);
+    Wgrad2Groups G;
+    int maxTotal = 1;
+    for (int i = 0; i < count; i++) {
+        if (int rc = wgrad2_check(&groups[i])) return rc;
+        G.g[i] = groups[i];
+        maxTotal = std::max(maxTotal, groups[i].K * (groups[i].N >> 2));
+    }
+    hipLaunchKernelGGL(dense_small_wgrad2_kernel, dim3(ceil_div(maxTotal, 256), count), dim3(256), 0, (hipStream_t)stream_, G);
+    IGAN_LAUNCH_CHECK("dense_small_wgrad2 launch");
+    return IGAN_OK;
+}
+
+extern "C" int igan_rows_group_sum(igan_stream_t stream_, const float* src, const int* slot, int count, float* out, int M, int L, int D) {
+    using namespace igan;
+    IGAN_REQUIRE(src && slot && out && count >= 1 && count <= IGAN_DENSE_MAX_GROUPS, "rows_group_sum: 1 <= count <= %d groups", IGAN_DENSE_MAX_GROUPS);
+    IGAN_REQUIRE(M >= 1 && L >= 1 && D >= 4 && D % 4 == 0 && (long long)M * L * D <= INT32_MAX, "rows_group_sum: D must be a positive multiple of 4");
+    IGAN_REQUIRE(((((uintptr_t)src) | ((uintptr_t)out)) & 15) == 0, "rows_group_sum: buffers must be 16-byte aligned");
+    RowsSumArgs A;
+    for (int i = 0; i < IGAN_DENSE_MAX_GROUPS; i++) A.slot[i] = i < count ? slot[i] : -1;
+    const int total = M * L * (D / 4);
+    hipLaunchKernelGGL(rows_group_sum_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, (hipStream_t)stream_, src, out, A, count, M, L, D / 4);
+    IGAN_LAUNCH_CHECK("rows_group_sum launch");
+    return IGAN_OK;
 }

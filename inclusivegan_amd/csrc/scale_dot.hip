@@ -105,6 +105,33 @@ __global__ __launch_bounds__(256) void scale_dot_final_kernel(const float* parti
     }
 }
 
+// out = a * alpha[n,c] + b * beta[n,c]: one pass where the second-order backward of the modulated convolution ran two or three
+// (g_t = g_dx s + x g_ds and its kin).  A float4 of channels per lane, four of them per thread with all loads in flight together.
+__global__ __launch_bounds__(256) void scale_add_kernel(const float4* a, const float* __restrict__ alpha, const float4* __restrict__ b,
+                                                        const float* __restrict__ beta, float4* out, int HWcv, int cv, int total) {
+    const int i0 = blockIdx.x * 1024 + threadIdx.x;
+    float4 x[4], y[4], sa[4], sb[4];
+    const float4 one = make_float4(1.f, 1.f, 1.f, 1.f), zero = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+        const int i = min(i0 + 256 * u, total - 1);      // clamped, masked at the store
+        const int n = i / HWcv, col = i % cv;
+        // uniform branches, not `p ? *p : constant`: that form is compiled as a select between two addresses, the constant's copy in scratch among them
+        x[u] = zero; y[u] = zero; sa[u] = one; sb[u] = one;
+        if (a) x[u] = a[i];
+        if (b) y[u] = b[i];
+        if (alpha) sa[u] = *reinterpret_cast<const float4*>(alpha + ((size_t)n * cv + col) * 4);
+        if (beta) sb[u] = *reinterpret_cast<const float4*>(beta + ((size_t)n * cv + col) * 4);
+    }
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+        const int i = i0 + 256 * u;
+        if (i < total)
+            out[i] = make_float4(fmaf(y[u].x, sb[u].x, x[u].x * sa[u].x), fmaf(y[u].y, sb[u].y, x[u].y * sa[u].y),
+                                 fmaf(y[u].z, sb[u].z, x[u].z * sa[u].z), fmaf(y[u].w, sb[u].w, x[u].w * sa[u].w));
+    }
+}
+
 int sd_blocks(int N, int HW, int C) {
     const int cvt = std::min(C / 4, 256);
     const int rl = 256 / cvt;
@@ -135,5 +162,20 @@ extern "C" int igan_scale_dot(igan_stream_t stream_, const float* a, const float
     hipLaunchKernelGGL(scale_dot_final_kernel, dim3(ceil_div(C, 16), N), dim3(256), 0, (hipStream_t)stream_,
                        (const float*)workspace, dot, blocks, C);
     IGAN_LAUNCH_CHECK("scale_dot launch");
+    return IGAN_OK;
+}
+
+extern "C" int igan_scale_add(igan_stream_t stream_, const float* a, const float* alpha, const float* b, const float* beta, float* out,
+                              int N, int HW, int C) {
+    using namespace igan;
+    IGAN_REQUIRE(out && (a || b), "scale_add: null buffer");
+    IGAN_REQUIRE(N >= 1 && HW >= 1 && C >= 4 && (C % 4) == 0, "scale_add: needs channel-minor data with C %% 4 == 0");
+    IGAN_REQUIRE((long long)N * HW * C <= INT32_MAX, "scale_add: tensor too large");
+    IGAN_REQUIRE((((uintptr_t)a | (uintptr_t)b | (uintptr_t)out | (uintptr_t)alpha | (uintptr_t)beta) & 15) == 0, "scale_add: buffers must be 16-byte aligned");
+    IGAN_REQUIRE(out != b, "scale_add: out may alias a, not b");
+    const int cv = C / 4, total = N * HW * cv;
+    hipLaunchKernelGGL(scale_add_kernel, dim3(ceil_div(total, 1024)), dim3(256), 0, (hipStream_t)stream_,
+                       reinterpret_cast<const float4*>(a), alpha, reinterpret_cast<const float4*>(b), beta, reinterpret_cast<float4*>(out), HW * cv, cv, total);
+    IGAN_LAUNCH_CHECK("scale_add launch");
     return IGAN_OK;
 }

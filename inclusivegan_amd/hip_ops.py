@@ -966,8 +966,8 @@ def matmul(x, w, alpha=1.0):
 # ----------------------------------------------------------------------------
 # modulated conv (fused scales on the first-order path)
 
-def scale_dot_raw(a, b, s=None, want_scaled=False):
-    """dot[n,c] = sum_hw a*b for channels_last a, b [N,C,H,W]; optionally also b*s[n,c] (written over b)."""
+def scale_dot_raw(a, b, s=None, want_scaled=False, keep_b=False):
+    """dot[n,c] = sum_hw a*b for channels_last a, b [N,C,H,W]; optionally also b*s[n,c] (written over b, or into a new tensor with keep_b)."""
     lib = _abi.get_plugin()
     _require_cuda_f32(a, b, s)
     a = nhwc(a)
@@ -977,9 +977,28 @@ def scale_dot_raw(a, b, s=None, want_scaled=False):
     ws = torch.empty((int(lib.igan_scale_dot_workspace_floats(n, h * w, c)),), device=a.device, dtype=torch.float32)
     if s is not None:
         s = s.contiguous()
-    _abi.check(lib.igan_scale_dot(_stream(), _ptr(a), _ptr(b), _ptr(s), _ptr(b) if want_scaled else ctypes.c_void_p(0),
-                                  _ptr(dot), _ptr(ws), n, h * w, c))
-    return dot, (b if want_scaled else None)
+    out = (torch.empty_like(b) if keep_b else b) if want_scaled else None
+    _abi.check(lib.igan_scale_dot(_stream(), _ptr(a), _ptr(b), _ptr(s), _ptr(out), _ptr(dot), _ptr(ws), n, h * w, c))
+    return dot, out
+
+
+def scale_add_raw(a, alpha, b, beta, inplace=False):
+    """a * alpha[n,c] + b * beta[n,c] for channels_last a, b [N,C,H,W] in one pass (igan_scale_add).  Either term may be None (at least one is given), a scale
+    of None is 1; `inplace` writes the result over (the channels_last form of) a."""
+    lib = _abi.get_plugin()
+    _require_cuda_f32(a, alpha, b, beta)
+    a = nhwc(a) if a is not None else None
+    b = nhwc(b) if b is not None else None
+    ref = a if a is not None else b
+    n, c, h, w = ref.shape
+    out = a if (inplace and a is not None) else torch.empty_like(ref)
+    alpha = alpha.contiguous() if alpha is not None else None
+    beta = beta.contiguous() if beta is not None else None
+    _abi.check(lib.igan_scale_add(_stream(), _ptr(a), _ptr(alpha), _ptr(b), _ptr(beta), _ptr(out), n, h * w, c))
+    return out
+
+
+_SCALE_ADD = os.environ.get('IGAN_SCALE_ADD', '1') != '0'      # A/B switch: 0 = the torch element-wise lines in ModConvGradFn.backward
 
 
 class ModConv2dFn(torch.autograd.Function):
@@ -1083,8 +1102,11 @@ class ModConvGradFn(torch.autograd.Function):
     def forward(ctx, dy, x, w, s, d, y, geom, in_hw, out_hw):
         dy = nhwc(dy)
         t = conv2d_raw(dy, w, dgrad_geom(geom), in_hw, w.shape[2], w_transposed=True, in_scale=d)
-        ds, _ = scale_dot_raw(x, t, None)
-        dx = t * s[:, :, None, None]
+        if _SCALE_ADD:
+            ds, dx = scale_dot_raw(x, t, s, want_scaled=True, keep_b=True)      # dx = t * s from the pass that sums ds; t itself is kept for the backward
+        else:
+            ds, _ = scale_dot_raw(x, t, None)
+            dx = t * s[:, :, None, None]
         dd = scale_dot_raw(dy, y)[0] / d
         ctx.save_for_backward(dy, x, w, s, d, y, t)
         ctx.geom, ctx.in_hw, ctx.out_hw = geom, in_hw, out_hw
@@ -1099,7 +1121,9 @@ class ModConvGradFn(torch.autograd.Function):
         need_dy, need_x, need_w, need_s, need_d = [_needed(ctx, i) for i in range(5)]
         g_dy = g_x = g_w = g_s = g_d = None
         if g_dx is not None or g_ds is not None:
-            if g_dx is not None:
+            if _SCALE_ADD:
+                g_t = scale_add_raw(g_dx, s, x if g_ds is not None else None, g_ds)      # g_dx * s + x * g_ds, one pass
+            elif g_dx is not None:
                 g_t = nhwc(g_dx) * s[:, :, None, None]
                 if g_ds is not None:
                     g_t = torch.addcmul(g_t, x, g_ds[:, :, None, None])
@@ -1113,21 +1137,27 @@ class ModConvGradFn(torch.autograd.Function):
                 g_w = conv2d_wgrad_raw(g_t, dy, geom, out_scale=d)
             if need_s and g_dx is not None:
                 g_s = scale_dot_raw(g_dx, t)[0]
-            if need_x and g_ds is not None:
+            if need_x and g_ds is not None and not (_SCALE_ADD and g_dd is not None):
                 g_x = t * g_ds[:, :, None, None]
         if g_dd is not None:
             g_dd = g_dd.contiguous()
             if need_x or need_s:
                 g_xs = conv2d_raw(dy, w, dgrad_geom(geom), ctx.in_hw, w.shape[2], w_transposed=True, in_scale=g_dd)
-                gs2, gx2 = scale_dot_raw(x, g_xs, s, want_scaled=need_x)
+                if _SCALE_ADD and need_x and g_ds is not None:
+                    gs2 = scale_dot_raw(x, g_xs)[0]
+                    g_x = scale_add_raw(t, g_ds, g_xs, s)      # t * g_ds + g_xs * s, one pass
+                else:
+                    gs2, gx2 = scale_dot_raw(x, g_xs, s, want_scaled=need_x)
+                    if need_x:
+                        g_x = gx2 if g_x is None else g_x + gx2
                 if need_s:
                     g_s = gs2 if g_s is None else g_s + gs2
-                if need_x:
-                    g_x = gx2 if g_x is None else g_x + gx2
             if need_w:
                 gw2 = conv2d_wgrad_raw(x, dy, geom, in_scale=s, out_scale=g_dd)
                 g_w = gw2 if g_w is None else g_w + gw2
-            if need_dy:
+            if need_dy and _SCALE_ADD:
+                g_dy = scale_add_raw(g_dy, None, y, g_dd / d, inplace=True)      # g_dy += y * (g_dd / d), in place, one pass
+            elif need_dy:
                 gdy2 = y * (g_dd / d)[:, :, None, None]
                 g_dy = gdy2 if g_dy is None else g_dy + gdy2
         return g_dy, g_x, g_w, g_s, g_d, None, None, None, None
@@ -1574,6 +1604,277 @@ def style_mod_all(layers):
     res = StyleModAllFn.apply(cfg, *flat)
     L = len(layers)
     dem = [i for i in range(L) if cfg[i][2]]
+    dmap = {i: res[L + j] for j, i in enumerate(dem)}
+    return [(res[i], dmap.get(i)) for i in range(L)]
+
+
+# ----------------------------------------------------------------------------
+# the style path of a pass that is differentiated twice (path-length step), closed: grouped kernels in all three directions
+
+_STYLE_CLOSED2 = os.environ.get('IGAN_STYLE_CLOSED2', '1') != '0'      # A/B switch: 0 = the per-layer composites under second_order()
+
+
+def dense_small2_grouped_raw(groups):
+    """One launch for a list of (igan_dense_params, e3, y2): include/igan_hip.h igan_dense_small2_grouped."""
+    lib = _abi.get_plugin()
+    arr = (_abi.Dense2Params * len(groups))(*[_abi.Dense2Params(p=p, e3=_ptr(e3).value, y2=_ptr(y2).value) for p, e3, y2 in groups])
+    _abi.check(lib.igan_dense_small2_grouped(_stream(), arr, len(groups)))
+
+
+def _wgrad2_group(a, b, dw, alpha=1.0, a2=None, pro_b=_abi.DENSE_PRO_NONE, b2=None, pro_scale=0.0, c=None, d=None, pro_c=_abi.DENSE_PRO_NONE, alpha2=0.0):
+    m, k = a.shape
+    return _abi.DenseWgrad2Params(a=a.data_ptr(), a2=_ptr(a2), b=b.data_ptr(), b2=_ptr(b2), c=_ptr(c), d=_ptr(d), dw=dw.data_ptr(), lda=a.stride(0),
+                                  ldc=c.stride(0) if c is not None else 0, M=m, K=k, N=b.shape[1], pro_b=pro_b, pro_c=pro_c,
+                                  alpha=float(alpha), pro_scale=float(pro_scale), alpha2=float(alpha2))
+
+
+def dense_small_wgrad2_grouped_raw(groups):
+    """dw = alpha * (a a2)^T . pro_b(b) + alpha2 * pro_c(c)^T . d per group, one launch (igan_dense_small_wgrad2_grouped)."""
+    lib = _abi.get_plugin()
+    arr = (_abi.DenseWgrad2Params * len(groups))(*groups)
+    _abi.check(lib.igan_dense_small_wgrad2_grouped(_stream(), arr, len(groups)))
+
+
+def rows_group_sum_raw(src, slots, L):
+    """src [count, M, D], slots[l] in [0, L) -> out [M, L, D] with out[:, j] = sum of the src[l] whose slot is j (igan_rows_group_sum)."""
+    lib = _abi.get_plugin()
+    _require_cuda_f32(src)
+    count, m, d = src.shape
+    out = torch.empty((m, L, d), device=src.device, dtype=torch.float32)
+    arr = (ctypes.c_int * count)(*[int(j) for j in slots])
+    _abi.check(lib.igan_rows_group_sum(_stream(), _ptr(src), arr, count, _ptr(out), m, L, d))
+    return out
+
+
+def _latent_rows(dlat, idx):
+    """dlat[:, idx] of a contiguous [N, L, D] tensor as a strided [N, D] kernel operand."""
+    return dlat[:, idx]
+
+
+def _style_sigma(cfg, act, wsqs, ss, dmap, gss, gds, ms=None, dbs=None):
+    """sigma = gs + 2 s (e . wsq^T), e = -c_w^2/2 gd d^3, for the layers `act` in one launch; optionally m = e . wsq^T and the bias gradients beside it."""
+    out = {}
+    groups = []
+    for i in act:
+        out[i] = torch.empty_like(ss[i])
+        p = _dense_group(gds[i], wsqs[i], out[i], w_transposed=True, prologue=_abi.DENSE_PRO_DEMOD_GRAD, x2=dmap[i], pro_scale=-0.5 * cfg[i][2] ** 2,
+                         epilogue=_abi.DENSE_EPI_STYLE_GRAD, e1=gss[i], e2=ss[i], bias_scale=1.0, colsum=dbs[i] if dbs is not None else None)
+        groups.append((p, None, ms[i] if ms is not None else None))
+    dense_small2_grouped_raw(groups)
+    return out
+
+
+class StyleGradAllFn(torch.autograd.Function):
+    """The latent gradient of the style path of one synthesis pass as ONE differentiable op (the backward of StyleAllClosedFn when it is differentiated again:
+    path-length regulariser, loss.py:60-66).  Per layer, with cotangents gs, gd on s = c_a y.A + b + 1 and d = rsqrt(c_w^2 s^2.W2 + 1e-8):
+        e = -1/2 c_w^2 gd d^3,   m = e.W2^T,   sigma = gs + 2 s m,   dy = c_a sigma.A^T     (summed over the layers a latent row feeds)
+    three grouped launches.  Its backward (one cotangent g on dy; not differentiable again), eight grouped launches for the whole network:
+        v = c_a g.A = gs_bar,   r = 2 v s,   e_bar = r.W2,   gd_bar = -1/2 c_w^2 d^3 e_bar,   q_bar = 3/4 c_w^2 gd d^5 e_bar
+        s_bar = 2 v m + 2 c_w^2 s (q_bar.W2^T),   W2_bar = r^T.e + c_w^2 (s s)^T.q_bar,   w_bar = 2 w W2_bar (every tap)
+        A_bar = c_a g^T.sigma + c_a y^T.s_bar,   b_bar = sum_n s_bar,   y_bar = c_a s_bar.A^T
+    (without demodulation, or without gd: sigma = gs, gs_bar = v, A_bar = c_a g^T.gs).  s and d come in as constants: the derivatives through them are the
+    s_bar / q_bar terms above.  cfg: (latent row, c_a, c_w, demodulate) per layer; tensors: dlat [N, L, D], then per layer (a_w, a_b, w, wsq), then s of every layer,
+    d of the demodulated ones, gs of every layer, gd of the demodulated ones (None where absent)."""
+
+    @staticmethod
+    def forward(ctx, cfg, dlat, *tensors):
+        _mark_inputs(ctx, cfg, dlat, *tensors)
+        L = len(cfg)
+        dem = [i for i in range(L) if cfg[i][3]]
+        nd = len(dem)
+        layers = [tensors[4 * i:4 * i + 4] for i in range(L)]
+        ss = tensors[4 * L:5 * L]
+        dmap = {i: tensors[5 * L + j] for j, i in enumerate(dem)}
+        gss = [g.contiguous() if g is not None else torch.zeros_like(ss[i]) for i, g in enumerate(tensors[5 * L + nd:6 * L + nd])]
+        gds = {i: tensors[6 * L + nd + j].contiguous() for j, i in enumerate(dem) if tensors[6 * L + nd + j] is not None}
+        act = [i for i in dem if i in gds]
+        n, nlat, dim = dlat.shape
+        ms = {i: torch.empty_like(ss[i]) for i in act}
+        sig = _style_sigma(cfg, act, {i: layers[i][3] for i in act}, ss, dmap, gss, gds, ms=ms) if act else {}
+        sigs = [sig.get(i, gss[i]) for i in range(L)]
+        a_ws = [layers[i][0].contiguous() for i in range(L)]
+        part = torch.empty((L, n, dim), device=dlat.device, dtype=torch.float32)
+        dense_small_grouped_raw([_dense_group(sigs[i], a_ws[i], part[i], w_transposed=True, alpha=cfg[i][1]) for i in range(L)])
+        dy = rows_group_sum_raw(part, [c[0] for c in cfg], nlat)
+        ctx.cfg, ctx.act = cfg, act
+        ctx.save_for_backward(dlat, *tensors[:5 * L + nd], *sigs, *[gds[i] for i in act], *[ms[i] for i in act])
+        return dy
+
+    @staticmethod
+    def backward(ctx, g):
+        if torch.is_grad_enabled():
+            raise NotImplementedError('style path: third-order gradients are not built')
+        cfg, act = ctx.cfg, ctx.act
+        L = len(cfg)
+        dem = [i for i in range(L) if cfg[i][3]]
+        nd, na = len(dem), len(act)
+        saved = ctx.saved_tensors
+        dlat, saved = saved[0], saved[1:]
+        layers = [saved[4 * i:4 * i + 4] for i in range(L)]
+        ss = saved[4 * L:5 * L]
+        dmap = {i: saved[5 * L + j] for j, i in enumerate(dem)}
+        sigs = saved[5 * L + nd:6 * L + nd]
+        gds = {i: saved[6 * L + nd + j] for j, i in enumerate(act)}
+        ms = {i: saved[6 * L + nd + na + j] for j, i in enumerate(act)}
+        n, nlat, dim = dlat.shape
+        dev = dlat.device
+        g = g.contiguous()
+        new = lambda *shape: torch.empty(shape, device=dev, dtype=torch.float32)
+        a_ws = [layers[i][0].contiguous() for i in range(L)]
+        # v = c_a g.A  (= gs_bar)
+        vs = [new(n, a_ws[i].shape[1]) for i in range(L)]
+        dense_small_grouped_raw([_dense_group(_latent_rows(g, cfg[i][0]), a_ws[i], vs[i], alpha=cfg[i][1]) for i in range(L)])
+        gdb, qb, sb, dbs, dws = {}, {}, {}, {}, {}
+        ybar = None
+        if act:
+            # e_bar = (2 v s).W2 with gd_bar and q_bar as its epilogue; s_bar (+ b_bar) from q_bar.W2^T
+            for i in act:
+                gdb[i], qb[i], sb[i], dbs[i] = torch.empty_like(gds[i]), torch.empty_like(gds[i]), torch.empty_like(ss[i]), new(ss[i].shape[1])
+            dense_small2_grouped_raw([(_dense_group(vs[i], layers[i][3], gdb[i], alpha=cfg[i][2] ** 2, prologue=_abi.DENSE_PRO_MUL, x2=ss[i], pro_scale=2.0,
+                                                    epilogue=_abi.DENSE_EPI_DEMOD_GRAD2, e1=gds[i], e2=dmap[i]), None, qb[i]) for i in act])
+            dense_small2_grouped_raw([(_dense_group(qb[i], layers[i][3], sb[i], w_transposed=True, alpha=cfg[i][2] ** 2, epilogue=_abi.DENSE_EPI_STYLE_GRAD2,
+                                                    e1=vs[i], e2=ss[i], bias_scale=1.0, colsum=dbs[i]), ms[i], None) for i in act])
+            # y_bar = c_a s_bar.A^T, summed per latent row
+            part = new(na, n, dim)
+            dense_small_grouped_raw([_dense_group(sb[i], a_ws[i], part[j], w_transposed=True, alpha=cfg[i][1]) for j, i in enumerate(act)])
+            ybar = rows_group_sum_raw(part, [cfg[i][0] for i in act], nlat)
+            # W2_bar and its spread onto the filter taps
+            wact = [i for i in act if ctx.needs_input_grad[2 + 4 * i + 2]]
+            if wact:
+                w2b = [torch.empty_like(layers[i][3]) for i in wact]
+                dense_small_wgrad2_grouped_raw([_wgrad2_group(vs[i], gds[i], w2b[j], alpha=2.0, a2=ss[i], pro_b=_abi.DENSE_PRO_DEMOD_GRAD, b2=dmap[i],
+                                                              pro_scale=-0.5 * cfg[i][2] ** 2, c=ss[i], d=qb[i], pro_c=_abi.DENSE_PRO_SQUARE, alpha2=cfg[i][2] ** 2)
+                                                for j, i in enumerate(wact)])
+                for i, t in zip(wact, bcast_mul_taps_grouped_raw([layers[i][2] for i in wact], w2b, 2.0)):
+                    dws[i] = t
+        # A_bar = c_a (g^T.sigma + y^T.s_bar)
+        das = [torch.empty_like(a_ws[i]) for i in range(L)]
+        dense_small_wgrad2_grouped_raw([_wgrad2_group(_latent_rows(g, cfg[i][0]), sigs[i], das[i], alpha=cfg[i][1],
+                                                      c=_latent_rows(dlat, cfg[i][0]) if i in sb else None, d=sb.get(i), alpha2=cfg[i][1]) for i in range(L)])
+        out = [None] * (6 * L + 2 * nd)
+        for i in range(L):
+            out[4 * i:4 * i + 3] = das[i], dbs.get(i), dws.get(i)
+            out[5 * L + nd + i] = vs[i]
+        for j, i in enumerate(dem):
+            out[6 * L + nd + j] = gdb.get(i)
+        out = [o if is_t else None for o, is_t in zip(out, ctx.input_is_tensor[2:])]      # a cotangent that came in as None takes no gradient
+        return (None, ybar, *out)
+
+
+class StyleAllClosedFn(torch.autograd.Function):
+    """StyleModAllFn for a pass that will be differentiated twice (hip_ops.second_order()): takes the latents whole, [N, L, D], and each layer's row of them, so
+    that the latent gradient is ONE tensor (no per-layer slice backward and no accumulation of their results).  Forward: the two grouped launches of
+    StyleModAllFn.  Backward: the grouped first-order kernels; under create_graph, when only the latent gradient is asked for (the path-length step), the closed
+    StyleGradAllFn, and the per-layer differentiable composite for every other request.  cfg: (latent row, c_a, c_w, demodulate) per layer; tensors per layer:
+    (a_w, a_b, w, wsq), w / wsq None without demodulation.  Returns s of every layer followed by d of the demodulated ones."""
+
+    @staticmethod
+    def forward(ctx, cfg, dlat, *tensors):
+        _mark_inputs(ctx, cfg, dlat, *tensors)
+        L = len(cfg)
+        layers = [tensors[4 * i:4 * i + 4] for i in range(L)]
+        n = dlat.shape[0]
+        dev = dlat.device
+        a_ws = [t[0].contiguous() for t in layers]
+        a_bs = [t[1].contiguous() for t in layers]
+        ss = [torch.empty((n, a_ws[i].shape[1]), device=dev, dtype=torch.float32) for i in range(L)]
+        dense_small_grouped_raw([_dense_group(_latent_rows(dlat, cfg[i][0]), a_ws[i], ss[i], alpha=cfg[i][1], epilogue=_abi.DENSE_EPI_BIAS, bias=a_bs[i], add_const=1.0)
+                                 for i in range(L)])
+        dem = [i for i in range(L) if cfg[i][3]]
+        ds = {i: torch.empty((n, layers[i][2].shape[3]), device=dev, dtype=torch.float32) for i in dem}
+        if dem:
+            dense_small_grouped_raw([_dense_group(ss[i], layers[i][3], ds[i], alpha=cfg[i][2] ** 2, prologue=_abi.DENSE_PRO_SQUARE,
+                                                  epilogue=_abi.DENSE_EPI_RSQRT, eps=1e-8) for i in dem])
+        ctx.cfg, ctx.dem = cfg, dem
+        ctx.save_for_backward(dlat, *tensors, *ss, *[ds[i] for i in dem])
+        return tuple(ss) + tuple(ds[i] for i in dem)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        cfg, dem = ctx.cfg, ctx.dem
+        L = len(cfg)
+        saved = ctx.saved_tensors
+        dlat, saved = saved[0], saved[1:]
+        layers = [saved[4 * i:4 * i + 4] for i in range(L)]
+        ss = saved[4 * L:5 * L]
+        dmap = {i: saved[5 * L + j] for j, i in enumerate(dem)}
+        gss = list(grads[:L])
+        gds = {i: grads[L + j] for j, i in enumerate(dem)}
+        need_lat = _needed(ctx, 1)
+        need = [[_needed(ctx, 2 + 4 * i + j) for j in range(3)] for i in range(L)]
+        out = [None] * (4 * L)
+        if torch.is_grad_enabled():
+            if need_lat and not any(any(nd) for nd in need):
+                # the path-length step: the latent gradient only, as the closed differentiable op
+                dy = StyleGradAllFn.apply(cfg, dlat, *saved[:4 * L], *[s.detach() for s in ss], *[dmap[i].detach() for i in dem], *gss, *[gds[i] for i in dem])
+                return (None, dy, *out)
+            # any other request: the differentiable per-layer composite
+            with torch.enable_grad():
+                outs, gouts, ins, where = [], [], [], []
+                for i in range(L):
+                    a_w, a_b, w, _ = layers[i]
+                    if gss[i] is None and gds.get(i) is None:
+                        continue
+                    sc, dc = style_mod_composite(dlat[:, cfg[i][0]], a_w, a_b, w, cfg[i][1], cfg[i][2], cfg[i][3])
+                    outs.append(sc); gouts.append(gss[i] if gss[i] is not None else torch.zeros_like(sc))
+                    if dc is not None and gds.get(i) is not None:
+                        outs.append(dc); gouts.append(gds[i])
+                    for j, t in enumerate((a_w, a_b, w)):
+                        if need[i][j] and t is not None:
+                            ins.append(t); where.append(4 * i + j)
+                if need_lat:
+                    ins.append(dlat); where.append(-1)
+                gr = torch.autograd.grad(outs, ins, gouts, create_graph=True, allow_unused=True) if outs and ins else []
+            dy = None
+            for k, t in zip(where, gr):
+                if k < 0:
+                    dy = t
+                else:
+                    out[k] = t
+            return (None, dy, *out)
+        dev = dlat.device
+        n, nlat, dim = dlat.shape
+        gss = [g.contiguous() if g is not None else torch.zeros_like(ss[i]) for i, g in enumerate(gss)]
+        gds = {i: g.contiguous() for i, g in gds.items() if g is not None}
+        act = [i for i in dem if i in gds]
+        dbs = {i: torch.empty((ss[i].shape[1],), device=dev, dtype=torch.float32) for i in act}
+        sig = _style_sigma(cfg, act, {i: layers[i][3] for i in act}, ss, dmap, gss, gds, dbs=dbs) if act else {}
+        if act:
+            dwsqs = [torch.empty_like(layers[i][3]) for i in act]
+            dense_small_wgrad_grouped_raw([_wgrad_group(ss[i], gds[i], dwsqs[j], pro_a=_abi.DENSE_PRO_SQUARE, pro_b=_abi.DENSE_PRO_DEMOD_GRAD,
+                                                        b2=dmap[i], pro_scale=-0.5 * cfg[i][2] ** 2) for j, i in enumerate(act)])
+            for i, t in zip(act, bcast_mul_taps_grouped_raw([layers[i][2] for i in act], dwsqs, 2.0)):
+                out[4 * i + 2] = t
+        sigs = [sig.get(i, gss[i]) for i in range(L)]
+        a_ws = [layers[i][0].contiguous() for i in range(L)]
+        part = torch.empty((L, n, dim), device=dev, dtype=torch.float32)
+        dense_small_grouped_raw([_dense_group(sigs[i], a_ws[i], part[i], w_transposed=True, alpha=cfg[i][1]) for i in range(L)])
+        dy = rows_group_sum_raw(part, [c[0] for c in cfg], nlat)
+        das = [torch.empty_like(a_ws[i]) for i in range(L)]
+        dense_small_wgrad_grouped_raw([_wgrad_group(_latent_rows(dlat, cfg[i][0]), sigs[i], das[i], alpha=cfg[i][1]) for i in range(L)])
+        for i in range(L):
+            out[4 * i] = das[i]
+            out[4 * i + 1] = dbs[i] if i in dbs else sigs[i].sum(dim=0)
+        return (None, dy, *out)
+
+
+def style_mod_all_closed(layers, dlat, rows):
+    """The styles of one synthesis pass under second_order() from the closed Functions: layers as for style_mod_all, dlat the latents whole [N, L, D], rows the
+    latent row of each layer.  None when they do not apply (switch, sizes, more than IGAN_DENSE_MAX_GROUPS layers): the caller takes the composites."""
+    if (not _STYLE_CLOSED2 or not layers or len(layers) > _abi.DENSE_MAX_GROUPS or _is_meta(dlat) or not dlat.is_cuda or dlat.dtype != torch.float32
+            or dlat.dim() != 3 or dlat.shape[2] % 4 != 0 or dlat.shape[0] > 64):
+        return None
+    dlat = dlat.contiguous()
+    for l in layers:
+        if not style_mod_fusable(dlat[:, 0], l['a_w'], l['w'], l['demodulate']):
+            return None
+    cfg = [(int(r), l['c_a'], l['c_w'], bool(l['demodulate'])) for l, r in zip(layers, rows)]
+    flat = []
+    for l in layers:
+        flat += [l['a_w'], l['a_b'], l['w'] if l['demodulate'] else None, l['wsq'] if l['demodulate'] else None]
+    res = StyleAllClosedFn.apply(cfg, dlat, *flat)
+    L = len(layers)
+    dem = [i for i in range(L) if cfg[i][3]]
     dmap = {i: res[L + j] for j, i in enumerate(dem)}
     return [(res[i], dmap.get(i)) for i in range(L)]
 

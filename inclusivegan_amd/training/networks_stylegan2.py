@@ -135,8 +135,9 @@ def naive_downsample_2d(x, factor=2):
 
 _STYLE_CACHE = []       # stack of {scope: (s, d)} of the synthesis passes being built
 
-def _precompute_styles(specs, dlatents, init_mul):
-    """specs: list of (scope path, layer index, cin, fmaps, kernel, demodulate) in call order."""
+def _precompute_styles(specs, dlatents, init_mul, dlatents_whole=None):
+    """specs: list of (scope path, layer index, cin, fmaps, kernel, demodulate) in call order; dlatents: the per-layer rows, dlatents_whole: the
+    [N, layers, D] tensor they were unbound from."""
     layers = []
     for scope, idx, cin, fmaps, kernel, demod in specs:
         names = scope.split('/')
@@ -162,7 +163,10 @@ def _precompute_styles(specs, dlatents, init_mul):
             l['wsq'] = v
     res = hip_ops.style_mod_all(layers)
     if res is None:
-        if hip_ops._second_order_depth > 0:       # path-length step: the differentiable composites, with what is common to the layers done once
+        if hip_ops._second_order_depth > 0 and dlatents_whole is not None:       # path-length step: grouped kernels closed under two differentiations
+            res = hip_ops.style_mod_all_closed(layers, dlatents_whole, [spec[1] for spec in specs])
+    if res is None:
+        if hip_ops._second_order_depth > 0:       # ... or the differentiable composites, with what is common to the layers done once
             b1 = hip_ops.style_bias_plus_one([l['a_b'] for l in layers])
             res = [hip_ops.style_mod_composite(l['y'], l['a_w'], l['a_b'], l['w'], l['c_a'], l['c_w'], l['demodulate'], b1=b1[i]) for i, l in enumerate(layers)]
         else:
@@ -445,6 +449,7 @@ def G_synthesis_stylegan2(
     batch = int(dlatents_in.shape[0])
     # One unbind (backward: one stack of the per-layer gradients) instead of a select per use, whose
     # backward is a zero-filled [N, layers, 512] tensor and an add each.
+    dlatents_whole = dlatents_in
     dlatents_in = dlatents_in.unbind(dim=1)
 
     # Noise inputs (:342-346).
@@ -500,7 +505,7 @@ def G_synthesis_stylegan2(
             specs.append((r + '/Conv1', res*2-4, nf(res-1), nf(res-1), 3, True))
             if architecture == 'skip' or res == resolution_log2:
                 specs.append((r + '/ToRGB', res*2-3, nf(res-1), num_channels, 1, False))
-        styles = _precompute_styles(specs, dlatents_in, init_mul)
+        styles = _precompute_styles(specs, dlatents_in, init_mul, dlatents_whole)
     _STYLE_CACHE.append(styles or {})
     try:
         # Early layers (:380-388).

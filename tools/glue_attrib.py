@@ -17,7 +17,7 @@ import op_profile  # noqa: E402
 from prof_summary import short  # noqa: E402
 
 OWN = ('conv_fwd', 'maxpool2x2', 'conv_wgrad_kernel', 'conv_fixup', 'plain_reduce', 'upfirdn2d', 'ban_', 'fba_kernel', 'scale_dot', 'lpips_kernel',
-       'mbstd', 'dense_small', 'thin_', 'adam', 'finite_check', 'ema_kernel', 'sumsq', 'bcast_mul', 'row_sqnorm', 'nn1', 'stamp', 'bias_grad')
+       'mbstd', 'dense_small', 'thin_', 'adam', 'finite_check', 'ema_kernel', 'sumsq', 'bcast_mul', 'row_sqnorm', 'nn1', 'stamp', 'bias_grad', 'rows_group_sum', 'scale_add')
 
 
 def main():
