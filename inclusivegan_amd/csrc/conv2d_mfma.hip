@@ -12,9 +12,12 @@
 // geometry, see include/igan_hip.h).  fp32 in, fp32 accumulate, like the reference
 // (dtype='float32', networks_stylegan2.py:264,323,422).
 //
-// A second, switchable form of the large 3x3 layers (IGAN_CONV_PLANES=1: conv_fwd_planes_kernel, conv_wgrad_planes_kernel, with
-// to_planes_kernel / filter_planes_kernel) runs the same products on the bf16 matrix instruction from three bf16 pieces per fp32
-// operand.  It is a labelled VARIANT, never selected unless the environment asks for it.
+// The large 3x3 layers run in a PIECE form: every fp32 operand is imaged once as two fp16 pieces and the
+// products run on the fp16 matrix instruction (conv_fwd_planes_w4_kernel, conv_fwd_planes_kernel<2, true>, conv_wgrad_planes_kernel<2>
+// with rows_f16_kernel / cols_f16_kernel / filter_planes_f16_kernel).  This is the default since round 4 (IGAN_CONV_PLANES unset or 2);
+// IGAN_CONV_PLANES=1 selects the earlier form on three bf16 pieces (conv_*_planes_kernel<3>, to_planes_kernel / filter_planes_kernel),
+// IGAN_CONV_PLANES=0 keeps every convolution on the fp32 instruction.  choose_fwd() / choose_wgrad() below are the ONE place that
+// decides which kernel a call takes.
 //
 // MI355X design (none of it is in the reference, which calls cuDNN):
 //  * activations are channel-minor [N,H,W,C]: an A-tile row (one output pixel, 32
@@ -51,9 +54,7 @@ namespace {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int BK = 32;        // reduction chunk (floats)
-#ifndef IGAN_SPLIT
-#define IGAN_SPLIT 8          // k steps (of 16) issued before the staged chunk is written to LDS: the lead time of the global loads
-#endif
+constexpr int LEAD_STEPS = 8; // k steps (of 16) issued before the staged chunk is written to LDS: the lead time of the global loads
 constexpr int LDK = BK + 4;   // row pitch of a [rows][k] LDS image (144 B: 16 B aligned, conflict-free b128 reads)
 
 struct ConvArgs {
@@ -77,10 +78,10 @@ struct ConvArgs {
     int vecY;               // 8 B output stores usable (Cout even, y / out_scale 8 B aligned)
     float alpha;            // output multiplier (applied here when splits == 1, else by the reduce kernel)
     int xcd_remap;          // XCD-aware block order (remap_xcd)
-    int b_scale;            // LDS-DMA kernel: one-sample tiles apply the modulation to the B fragments (A/B switch IGAN_CONV_BSCALE)
-    int prio;               // LDS-DMA kernel: raised issue priority during the tile prologue (A/B switch IGAN_CONV_PROLOGUE_PRIO)
+    int b_scale;            // LDS-DMA kernel: one-sample tiles apply the modulation to the B fragments (the host always sets 1)
+    int prio;               // LDS-DMA and piece kernels: raised issue priority during the tile prologue (the host always sets 1)
     int walk;               // walking address computation usable (16 B paths, Cin % 32 == 0)
-    int stagger;            // start delay (64-cycle quanta) of the workgroup in the upper LDS slot (0 = none)
+    int stagger;            // start delay (64-cycle quanta) of the workgroup in the upper LDS slot (the host always sets 0 = none)
     unsigned long long* diag;   // diagnostic build-in: 4 time stamps (100 MHz ticks) per workgroup, or nullptr
     const float* bias;      // fused epilogue (act != 0): y = act(y + noise[n, pixel] * strength + bias[co]) * act_gain
     int act;                // 0 none, 1 linear, 2 relu, 3 lrelu
@@ -88,7 +89,7 @@ struct ConvArgs {
     const float* noise;     // [N or 1, OH, OW] or nullptr; strength = *noise_strength (device scalar)
     const float* noise_strength;
     int noise_bcast;        // noise has one sample, shared by the batch
-    int diag_mode;              // IGAN_DIAGNOSTIC builds only (tools/coresidency_probe.py): bit mask of parts of conv_fwd_planes_kernel<2> to leave out; 0 in the product
+    int diag_mode;              // unused (the host always sets 0); kept so that the kernel-argument offsets of the fields behind it do not move
     const unsigned short* xp;   // bf16-piece form (conv_fwd_planes_kernel): x * in_scale as [pixel][Cin/16][3 pieces][16] bf16
     const unsigned short* wp;   //   and the filter as [tap][n][Cin/16][3][16] (the orientation is resolved when it is written)
 };
@@ -496,12 +497,6 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 16) ? 8 : ((WM * WN == 8)
     }
     __syncthreads();
     stamp(1);
-#ifdef IGAN_YOUNG_PRIO
-    // The second-dispatched half of an 8-wave workgroup (waves 4-7: one per SIMD, beside waves 0-3) loses every issue
-    // arbitration to its older partner, arrives late at each chunk's barrier and makes the older half wait there (measured per
-    // chunk: older waves 1370 cycles at the barrier, younger ones 270).  A static priority for the younger half evens it out.
-    if (WM * WN == 8 && wave >= 4) __builtin_amdgcn_s_setprio(IGAN_YOUNG_PRIO);
-#endif
 #ifdef IGAN_LOOP_STAMPS
     // Diagnostic variant (make variant DEFS=-DIGAN_LOOP_STAMPS): per wave, the shader cycles spent in the four phases of a
     // chunk, summed over the tile's chunks: [top .. first MFMA half issued] [.. staged chunk written to LDS] [.. second MFMA
@@ -521,7 +516,7 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 16) ? 8 : ((WM * WN == 8)
         float af[TM][16], bf[TN][16];
         load_frag<TM, false, LDK>(As + cur * A_ELEMS, wm * (BM / WM), l31, h, af);
         load_frag<TN, !WT, LDB>(Bs + cur * B_ELEMS, wn * (BN / WN), l31, h, bf);
-        mma_steps<TM, TN, 0, IGAN_SPLIT>(af, bf, acc);
+        mma_steps<TM, TN, 0, LEAD_STEPS>(af, bf, acc);
         LOOP_STAMP(ts1)
         prep_chunk(c + 2 < c_end);           // addresses of chunk c+2: VALU only, free to interleave with the MFMAs
         // ... and its consumers (with their s_waitcnt vmcnt) stay BEHIND the first half of the MFMAs:
@@ -532,7 +527,7 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 16) ? 8 : ((WM * WN == 8)
         __builtin_amdgcn_sched_barrier(0);
         store_chunk(cur ^ 1);
         LOOP_STAMP(ts2)
-        mma_steps<TM, TN, IGAN_SPLIT, 16>(af, bf, acc);
+        mma_steps<TM, TN, LEAD_STEPS, 16>(af, bf, acc);
         LOOP_STAMP(ts3)
         __syncthreads();
 #ifdef IGAN_LOOP_STAMPS
@@ -640,15 +635,8 @@ __device__ __forceinline__ int div_small(int m, int d, float inv) {
 //  * The modulation scale is applied to the A fragments after the LDS read (the products x*s are the same single roundings as
 //    in the staged kernel); the scale rows of the samples the tile touches sit in LDS (at most 2048 floats: the host checks),
 //    and 16 B paths with Cin % 32 == 0 (`walk`) are required.
-//  * PIECES = 2 / 3 (measure-only variants behind IGAN_CONV_BF16X3=1 / =6, never the default): the fp32 fragments are split in
-//    registers into bf16 pieces, x = x0 + x1 (+ x2) with x0 = bf16(x), x1 = bf16(x - x0), ..., and a product runs as the three
-//    (a1 b0 + a0 b1 + a0 b0) or six (all a_i b_j, i + j <= 2) v_mfma_f32_32x32x16_bf16 with fp32 accumulation instead of eight
-//    v_mfma_f32_32x32x2_f32: 12 / 24 matrix instructions of 32 cycles per chunk and wave instead of 32 of 64.  Not fp32-exact
-//    (two pieces: ~7x the rounding error of the fp32 FMA chain; three: about the chain's); the accumulator layout, and with it the
-//    whole epilogue, is the same.  A lane's eight k values of a 16-deep step are quarters (2s, 2s+1) of its half.
-template <bool WT, bool SC, int PIECES = 0>      // PIECES: 0 = fp32 MFMA (the product path), 2 / 3 = bf16 pieces per operand (measure-only)
+template <bool WT, bool SC>
 __global__ __launch_bounds__(512, 4) void conv_fwd_dma_kernel(ConvArgs a) {
-    constexpr bool SPLIT = PIECES != 0;
     constexpr int BM = 128, BN = 128, WN = 4, TM = 2, TN = 1;
     constexpr int A_STAGE = BM * BK, B_STAGE = BK * BN;          // floats per stage (16 KiB each)
     constexpr int SMAX = 2048;                                   // scale rows of the tile's samples: (samples per tile) * Cin <= SMAX, checked by the host
@@ -828,50 +816,6 @@ __global__ __launch_bounds__(512, 4) void conv_fwd_dma_kernel(ConvArgs a) {
                 acc[tm][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(afq[q][tm][j], bfq[q][j], acc[tm][0], 0, 0, 0);
     };
     auto next_ci = [&](int ci) { return (ci + 1 == a.cpt) ? 0 : ci + 1; };
-    typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-    constexpr int NP = SPLIT ? PIECES : 1;
-    auto split8 = [&](const float (&lo4)[4], const float (&hi4)[4], bf16x8 (&pc)[NP]) {
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-            float r = j < 4 ? lo4[j] : hi4[j - 4];
-#pragma unroll
-            for (int p = 0; p < NP; p++) {
-                const __bf16 b = (__bf16)r;              // v_cvt_pk_bf16_f32: round to nearest even
-                pc[p][j] = b;
-                if (p + 1 < NP) r -= (float)b;
-            }
-        }
-    };
-    auto mma_split_step = [&](int s) {       // k step s of the chunk: quarters 2s, 2s+1
-        bf16x8 b[NP];
-        split8(bfq[2 * s], bfq[2 * s + 1], b);
-#pragma unroll
-        for (int tm = 0; tm < TM; tm++) {
-            bf16x8 av[NP];
-            split8(afq[2 * s][tm], afq[2 * s + 1][tm], av);
-            // all products a_i b_j with i + j < PIECES, smallest first
-#ifdef IGAN_SPLIT_PROMOTE      // experiment: the step's products are summed from zero and added to the running sum by the vector ALU (RN)
-            f32x16 t;
-#pragma unroll
-            for (int r = 0; r < 16; r++) t[r] = 0.0f;
-#pragma unroll
-            for (int oo = 0; oo < NP; oo++) {
-                const int o = (IGAN_SPLIT_PROMOTE == 2) ? oo : NP - 1 - oo;       // 2: largest products first (the addend is never the small term)
-#pragma unroll
-                for (int i = 0; i <= o; i++)
-                    t = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[i], b[o - i], t, 0, 0, 0);
-            }
-#pragma unroll
-            for (int r = 0; r < 16; r++) acc[tm][0][r] += t[r];
-#else
-#pragma unroll
-            for (int o = NP - 1; o >= 0; o--)
-#pragma unroll
-                for (int i = 0; i <= o; i++)
-                    acc[tm][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[i], b[o - i], acc[tm][0], 0, 0, 0);
-#endif
-        }
-    };
 
 #ifdef IGAN_PROLOGUE_STAMPS      // diagnostic build: slot 1 = tables computed / first DMA about to be issued, slot 2 = first barrier passed
     stamp(1);
@@ -930,26 +874,16 @@ __global__ __launch_bounds__(512, 4) void conv_fwd_dma_kernel(ConvArgs a) {
             __builtin_amdgcn_sched_barrier(0);
             read_q(bs_tag, cur, 2, sc_ci);
             read_q(bs_tag, cur, 3, sc_ci);
-            if constexpr (SPLIT) {
-                mma_split_step(0);
-            } else {
-                mma_q(0);
-                mma_q(1);
-                mma_q(2);
-            }
+            mma_q(0);
+            mma_q(1);
+            mma_q(2);
             __builtin_amdgcn_sched_barrier(0);
             __syncthreads();                     // vmcnt(0) lgkmcnt(0) + barrier: chunk c+1 landed, everyone done reading stage `cur`
             __builtin_amdgcn_sched_barrier(0);
             sc_ci = next_ci(sc_ci);
-            if constexpr (SPLIT) {
-                mma_split_step(1);               // quarters 2, 3 (read before the barrier) while the next chunk's first reads land
-                read_q(bs_tag, cur ^ 1, 0, sc_ci);
-                read_q(bs_tag, cur ^ 1, 1, sc_ci);
-            } else {
-                read_q(bs_tag, cur ^ 1, 0, sc_ci);
-                read_q(bs_tag, cur ^ 1, 1, sc_ci);
-                mma_q(3);
-            }
+            read_q(bs_tag, cur ^ 1, 0, sc_ci);
+            read_q(bs_tag, cur ^ 1, 1, sc_ci);
+            mma_q(3);
             __builtin_amdgcn_sched_barrier(0);
         }
     };
@@ -1244,9 +1178,6 @@ __device__ __forceinline__ float inv_scale_from_amax(float amax) {
     return __uint_as_float((unsigned)(e - 14) << 23);
 }
 __device__ __forceinline__ void count_window(int below, unsigned long long* counter) {      // per wave: one atomic when anything is to be counted (diagnostic)
-#ifdef IGAN_NO_WINDOW_COUNT
-    return;
-#endif
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) below += __shfl_xor(below, o);
     if ((threadIdx.x & 63) == 0 && below != 0) atomicAdd(counter, (unsigned long long)below);
@@ -1330,9 +1261,7 @@ __global__ __launch_bounds__(256) void rows_f16_kernel(const float* __restrict__
         store_units(pc, stage, out, total, chunk);
     }
     count_window(below, &g_f16_below_window);
-#ifndef IGAN_NO_WINDOW_COUNT
     if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&g_f16_imaged, (unsigned long long)total * 16ull);
-#endif
     if (colmax != nullptr) {        // wave-uniform
         __syncthreads();
         float* sm = reinterpret_cast<float*>(stage);            // [256 threads][16]
@@ -1426,9 +1355,7 @@ __global__ __launch_bounds__(256) void cols_f16_kernel(const float* __restrict__
         below += (mine && vs != 0.0f && fabsf(vs) < 0x1p-12f) ? 1 : 0;
     }
     count_window(below, &g_f16_below_window_cols);
-#ifndef IGAN_NO_WINDOW_COUNT
     if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&g_f16_imaged_cols, (unsigned long long)total * 16ull);
-#endif
     store_units(pc, stage, out, total, (int)blockIdx.x);
 }
 
@@ -1522,34 +1449,23 @@ __global__ __launch_bounds__(256) void filter_planes_f16_kernel(const float* __r
         }
 }
 
-// TAPO (fp16 form only): the reduction runs TAP outermost, the 16-channel slices of a tap inside it.  A row's pixel -- and with it the row's scale --
+// TAPO (the fp16 form, NP == 2): the reduction runs TAP outermost, the 16-channel slices of a tap inside it.  A row's pixel -- and with it the row's scale --
 // then stays the same for Cin / 16 consecutive steps, so the cross terms are chained in the matrix pipe over a tap and folded once per tap
-// (32 vector instructions per step instead of 64).  !TAPO: slice outermost, taps inside (the taps of a slice re-read the same shifted rows back to
-// back); every step folds its own cross terms.  Same products and the same per-step rounding of the main term either way; which one a layer takes is
-// a measured choice (igan_conv2d: IGAN_F16_TAP_OUTER).
+// (32 vector instructions per step instead of 64; profiles/r05_f16_rowscale.txt).  !TAPO (the bf16 form, NP == 3): slice outermost, taps inside
+// (the taps of a slice re-read the same shifted rows back to back).  These two are the only instantiations.
 template <int NP, bool TAPO = false>
 __global__ __launch_bounds__(512, 4) void conv_fwd_planes_kernel(ConvArgs a) {
     constexpr int BM = 128, BN = 128, WN = 4, TM = 2;
-    static_assert(NP == 3 || NP == 2, "three bf16 pieces (six products) or two fp16 pieces (three products)");
+    static_assert((NP == 3 && !TAPO) || (NP == 2 && TAPO), "three bf16 pieces (six products, slice outermost) or two fp16 pieces (three products, tap outermost)");
     constexpr int IMG = NP * 128 * 32, STAGE = 2 * IMG;       // one operand's LDS image [NP pieces][128 rows][32 B]; a stage = A + B
     constexpr unsigned PB = NP * 32u;                          // bytes of one (pixel, 16-channel slice) in a piece image
     constexpr int TABS = (NP == 2) ? 9 * BM * 4 : 0;           // fp16 form: 1 / S of the input pixel each (tap, tile row) reads (at most 3x3 taps)
-#ifndef IGAN_F16_LDS_PAD
-#define IGAN_F16_LDS_PAD 0
-#endif
-    constexpr int LPAD = (NP == 2) ? IGAN_F16_LDS_PAD : 0;     // experiment: pad the fp16 tile's LDS footprint (co-residency with other kernels)
-    __shared__ __attribute__((aligned(1024))) unsigned char smem[P_NSTAGE * STAGE + 3 * BM * 4 + TABS + LPAD];
+    __shared__ __attribute__((aligned(1024))) unsigned char smem[P_NSTAGE * STAGE + 3 * BM * 4 + TABS];
     int* row_pix = reinterpret_cast<int*>(smem + P_NSTAGE * STAGE);
     int* row_n = row_pix + BM;
     float* row_nz = reinterpret_cast<float*>(row_n + BM);
     float* tab_s = row_nz + BM;
 
-#ifdef IGAN_DIAGNOSTIC
-    const int dm = a.diag_mode;
-    if (dm & 4) return;
-#else
-    constexpr int dm = 0;
-#endif
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // wave-uniform: kept in a scalar register
     const int l31 = lane & 31, h = lane >> 5;
@@ -1741,11 +1657,11 @@ __global__ __launch_bounds__(512, 4) void conv_fwd_planes_kernel(ConvArgs a) {
             }
         }
     }
-    if ((c_begin < c_end) && !(dm & 32)) { dma_chunk(0); dma_chunk(1); }
+    if (c_begin < c_end) { dma_chunk(0); dma_chunk(1); }
     if constexpr (NP == 2) {
 #pragma unroll
         for (int j = 0; j < 3; j++)
-            if (tid + 512 * j < 9 * BM && !(dm & 64)) tab_s[tid + 512 * j] = tabv[j];
+            if (tid + 512 * j < 9 * BM) tab_s[tid + 512 * j] = tabv[j];
     }
     // the epilogue's row tables, computed while the first chunks are in flight
     if (tid < BM) {
@@ -1780,7 +1696,7 @@ __global__ __launch_bounds__(512, 4) void conv_fwd_planes_kernel(ConvArgs a) {
         // (l31) and its 16 registers are output channels (r & 3) + 8 (r >> 2) + 4 h of the wave's 32 -- the pixel's 1 / S is one value per lane
         // and tile, and the epilogue stores 16 B per register quad.
         const float* tab_row = tab_s + wm * 64 + l31;
-        if constexpr (TAPO) {
+        {
             int ct = (c_begin < c_end) ? c_begin / a.cpt : 0;                       // tap of the chunk being consumed
             int cs = (c_begin < c_end) ? c_begin - ct * a.cpt : 0;                  // its slice
             bool cs_new = true;
@@ -1790,8 +1706,10 @@ __global__ __launch_bounds__(512, 4) void conv_fwd_planes_kernel(ConvArgs a) {
             for (int tm = 0; tm < TM; tm++)
 #pragma unroll
                 for (int r = 0; r < 16; r++) u[tm][r] = 0.0f;
-            for (int c = (dm & 8) ? c_end : c_begin; c < c_end; c++) {
-                asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)\n\ts_barrier" ::: "memory");     // as below
+            for (int c = c_begin; c < c_end; c++) {
+                // chunk c landed (two younger instructions: chunk c+1); stage st+2 is free.  lgkmcnt(0): the first barrier also publishes the scale table
+                // (every wave's ds_write has completed before it arrives); later iterations have no LDS operation in flight at this point.
+                asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)\n\ts_barrier" ::: "memory");
                 const int nst = st >= 1 ? st - 1 : P_NSTAGE - 1;
                 const unsigned char* S = smem + st * STAGE;
                 f16x8 a0[TM], a1[TM];
@@ -1810,7 +1728,7 @@ __global__ __launch_bounds__(512, 4) void conv_fwd_planes_kernel(ConvArgs a) {
                 u[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(b1, a0[0], u[0], 0, 0, 0);
                 u[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(b1, a0[1], u[1], 0, 0, 0);
                 __builtin_amdgcn_sched_barrier(0);
-                if (!(dm & 32)) { dma_piece(0); dma_piece(1); }            // chunk c + 2, issued inside the matrix cluster
+                dma_piece(0); dma_piece(1);                                // chunk c + 2, issued inside the matrix cluster
 #pragma unroll
                 for (int r = 0; r < 16; r++) acc[0][r] = __builtin_fmaf(t[r], sc0, acc[0][r]);        // vector ALU: round to nearest
                 __builtin_amdgcn_sched_barrier(0);
@@ -1831,48 +1749,9 @@ __global__ __launch_bounds__(512, 4) void conv_fwd_planes_kernel(ConvArgs a) {
                 }
                 st = (st + 1 == P_NSTAGE) ? 0 : st + 1;
             }
-        } else {
-        int ct = (c_begin < c_end) ? c_begin - (c_begin / ntap) * ntap : 0;      // tap of the chunk being consumed (the reduction runs slice outermost, taps inside)
-        for (int c = c_begin; c < c_end; c++) {
-            // chunk c landed (two younger instructions: chunk c+1); stage st+2 is free.  lgkmcnt(0): the first barrier also publishes the scale table
-            // (every wave's ds_write has completed before it arrives); later iterations have no LDS operation in flight at this point.
-            asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-            const int nst = st >= 1 ? st - 1 : P_NSTAGE - 1;
-            const unsigned char* S = smem + st * STAGE;
-            f16x8 a0[TM], a1[TM];
-            const f16x8 b0 = __builtin_bit_cast(f16x8, *reinterpret_cast<const bf16x8*>(S + fb));
-            const f16x8 b1 = __builtin_bit_cast(f16x8, *reinterpret_cast<const bf16x8*>(S + fb + 4096));
-#pragma unroll
-            for (int tm = 0; tm < TM; tm++) {
-                a0[tm] = __builtin_bit_cast(f16x8, *reinterpret_cast<const bf16x8*>(S + fa[tm]));
-                a1[tm] = __builtin_bit_cast(f16x8, *reinterpret_cast<const bf16x8*>(S + fa[tm] + 4096));
-            }
-            const float sc0 = tab_row[ct * BM], sc1 = tab_row[ct * BM + 32];
-            ct = (ct + 1 == ntap) ? 0 : ct + 1;
-            dma_prep(nst);
-            // One set of 32 registers (main term t, cross terms v) serves both 32x32 tiles of the wave: every product chain of a step starts from an exact
-            // zero, and (t + 2^-11 v) / S_pixel is added to the running sum by the vector ALU (round to nearest).
-            f32x16 t, v;
-            __builtin_amdgcn_sched_barrier(0);
-            t = __builtin_amdgcn_mfma_f32_32x32x16_f16(b0, a0[0], zero, 0, 0, 0);
-            v = __builtin_amdgcn_mfma_f32_32x32x16_f16(b1, a0[0], zero, 0, 0, 0);
-            v = __builtin_amdgcn_mfma_f32_32x32x16_f16(b0, a1[0], v, 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-            dma_piece(0); dma_piece(1);             // chunk c + 2, issued inside the matrix cluster
-#pragma unroll
-            for (int r = 0; r < 16; r++) acc[0][r] = __builtin_fmaf(__builtin_fmaf(v[r], 1.0f / 2048.0f, t[r]), sc0, acc[0][r]);
-            __builtin_amdgcn_sched_barrier(0);
-            t = __builtin_amdgcn_mfma_f32_32x32x16_f16(b0, a0[1], zero, 0, 0, 0);
-            v = __builtin_amdgcn_mfma_f32_32x32x16_f16(b1, a0[1], zero, 0, 0, 0);
-            v = __builtin_amdgcn_mfma_f32_32x32x16_f16(b0, a1[1], v, 0, 0, 0);
-#pragma unroll
-            for (int r = 0; r < 16; r++) acc[1][r] = __builtin_fmaf(__builtin_fmaf(v[r], 1.0f / 2048.0f, t[r]), sc1, acc[1][r]);
-            st = (st + 1 == P_NSTAGE) ? 0 : st + 1;
-        }
         }
         drain_lds_dma();
         stamp(2);
-        if (dm & 16) return;
         // ---- epilogue of the transposed tile: every register quad is four consecutive output channels of the lane's pixel ----
         // 1 / S_n of the filter's columns (exact: a power of two), then as in conv_fwd_dma_kernel
         const float* winv = reinterpret_cast<const float*>(reinterpret_cast<const unsigned char*>(a.wp) + (size_t)a.KH * a.KW * a.Cin * a.Cout * 4);
@@ -2651,10 +2530,7 @@ typedef __attribute__((ext_vector_type(4))) short s16x4;
 // `s_waitcnt vmcnt(0)` in front of those reads in every step: each wave then waited for the chunk it had issued ONE step earlier, i.e. the
 // two-deep prefetch was one deep.  (The forward kernel's plain ds_read_b128 do not get that wait.)  Issued from assembly the DMA is invisible to
 // the compiler's counters and the kernel's own `s_waitcnt vmcnt(NP)` in front of the barrier is the only wait, as designed; vector-memory
-// instructions the compiler does count (the epilogue's stores) only ever wait longer for it.  -DIGAN_WGRAD_ASM_DMA=0 restores the builtin.
-#ifndef IGAN_WGRAD_ASM_DMA
-#define IGAN_WGRAD_ASM_DMA 1
-#endif
+// instructions the compiler does count (the epilogue's stores) only ever wait longer for it.
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ u32x4 raw_rsrc_words(const void* base, unsigned bytes) {     // the words __builtin_amdgcn_make_buffer_rsrc(base, 0, bytes, 0x00020000) makes
     const unsigned long long b = (unsigned long long)(uintptr_t)base;
@@ -2762,7 +2638,6 @@ __global__ __launch_bounds__(512, 4) void conv_wgrad_planes_kernel(WgradArgs a) 
         linA += dA0 + (c1 ? dA1 : 0u) + (c2 ? dA2 : 0u);
         linB += dB0 + (c1 ? dB1 : 0u) + (c2 ? dB2 : 0u);
     };
-#if IGAN_WGRAD_ASM_DMA
     const u32x4 wx = raw_rsrc_words(a.xp, xbytes), wdy = raw_rsrc_words(a.dyp, dybytes);
     auto dma_piece = [&](int j) {       // as in conv_fwd_planes_kernel: waves 0-3 A pieces 0, 2 and B piece 1; waves 4-7 A piece 1 and B pieces 0, 2 (NP == 2: A 0, B 1 / A 1, B 0)
         const unsigned A = (unsigned)(uintptr_t)(lds_void*)dA, B = A + IMG;
@@ -2785,31 +2660,6 @@ __global__ __launch_bounds__(512, 4) void conv_wgrad_planes_kernel(WgradArgs a) 
             if (j == 2) lds_dma16_asm<64>(wdy, B + 2 * 4096, offB);
         }
     };
-#else
-    auto dma_piece = [&](int j) {       // as in conv_fwd_planes_kernel: waves 0-3 A pieces 0, 2 and B piece 1; waves 4-7 A piece 1 and B pieces 0, 2
-        unsigned char* A = dA;
-        unsigned char* B = dA + IMG;
-        if constexpr (NP == 2) {        // waves 0-3 A piece 0 and B piece 1, waves 4-7 A piece 1 and B piece 0
-            if (lowave) {
-                if (j == 0) __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (lds_void*)A, 16, offA, 0, 0, 0);
-                if (j == 1) __builtin_amdgcn_raw_ptr_buffer_load_lds(rdy, (lds_void*)(B + 4096), 16, offB, 32, 0, 0);
-            } else {
-                if (j == 0) __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (lds_void*)(A + 4096), 16, offA, 32, 0, 0);
-                if (j == 1) __builtin_amdgcn_raw_ptr_buffer_load_lds(rdy, (lds_void*)B, 16, offB, 0, 0, 0);
-            }
-        } else
-        if (lowave) {
-            if (j == 0) __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (lds_void*)A, 16, offA, 0, 0, 0);
-            if (j == 1) __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (lds_void*)(A + 2 * 4096), 16, offA, 64, 0, 0);
-            if (j == 2) __builtin_amdgcn_raw_ptr_buffer_load_lds(rdy, (lds_void*)(B + 4096), 16, offB, 32, 0, 0);
-        } else {
-            if (j == 0) __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (lds_void*)(A + 4096), 16, offA, 32, 0, 0);
-            if (j == 1) __builtin_amdgcn_raw_ptr_buffer_load_lds(rdy, (lds_void*)B, 16, offB, 0, 0, 0);
-            if (j == 2) __builtin_amdgcn_raw_ptr_buffer_load_lds(rdy, (lds_void*)(B + 2 * 4096), 16, offB, 64, 0, 0);
-        }
-    };
-
-#endif
     // ---- transposed fragment reads: lane 16 g + 4 q + p supplies row q, columns 4 p .. 4 p + 3 of its group's block
     // (k group g >> 1, channels 16 (g & 1) .. + 15 of the 32-wide fragment); the second read takes the block four rows below
     const int tg = lane >> 4, tq = (lane >> 2) & 3, tp = lane & 3;
@@ -2987,14 +2837,10 @@ int fwd_geometry_check(const igan_conv2d_params* p) {
     return IGAN_OK;
 }
 
-// The 128x128 (and 128x64) tile runs with 8 wavefronts (2 x 4 of 64x32 accumulators, two per SIMD, four with both resident
+// The fp32 128x128 (and 128x64) tile runs with 8 wavefronts (2 x 4 of 64x32 accumulators, two per SIMD, four with both resident
 // workgroups) rather than 4 (2 x 2 of 64x64): the matrix pipe of a SIMD then always has a second wave of the
 // same workgroup to issue from while one waits on LDS or the barrier (+3 % on the layer mix, more for a
-// workgroup that is alone on its CU).  IGAN_CONV_8WAVE=0 / IGAN_WGRAD_8WAVE=0 select the 4-wave form (A/B runs).
-bool eight_waves(const char* env) {
-    const char* v = getenv(env);
-    return !(v && atoi(v) == 0);
-}
+// workgroup that is alone on its CU).
 
 // 1x1 convolution on a 1x1 map = a dense layer; with at most 32 rows and no scales it goes to dense_small.hip
 bool is_small_dense(const igan_conv2d_params* p) {
@@ -3065,11 +2911,11 @@ TileList tile_list(const igan_conv2d_params* p, const FwdTile& t, int Mmax, int 
 }
 
 
-// Does this launch take the LDS-DMA form of the 128x128 tile (conv_fwd_dma_kernel)?  16 B paths with Cin % 32 == 0, 8-wave
-// tiles, and -- when an input scale is present -- the scale rows of the samples one tile can touch fitting its LDS table.
+// Does this launch take the LDS-DMA form of the 128x128 tile (conv_fwd_dma_kernel)?  16 B paths with Cin % 32 == 0 (`walk`)
+// and -- when an input scale is present -- the scale rows of the samples one tile can touch fitting its LDS table.
 bool use_dma_kernel(const igan_conv2d_params* p, const FwdTile& t, bool walk) {
     static const bool dma = !(getenv("IGAN_CONV_DMA") && atoi(getenv("IGAN_CONV_DMA")) == 0);      // A/B switch
-    if (!dma || t.BM != 128 || t.BN != 128 || !walk || !eight_waves("IGAN_CONV_8WAVE")) return false;
+    if (!dma || t.BM != 128 || t.BN != 128 || !walk) return false;
     if ((long long)p->N * p->OH * p->OW >= (1LL << 24)) return false;          // the kernel's row decode divides in float (div_small)
     if (p->in_scale) {      // the scale rows of all samples a tile can touch must fit the kernel's LDS table (2048 floats)
         const int up = p->up;
@@ -3083,13 +2929,10 @@ bool use_dma_kernel(const igan_conv2d_params* p, const FwdTile& t, bool walk) {
     return true;
 }
 
-bool walk_ok(const igan_conv2d_params* p) {
-    static const bool walk = !(getenv("IGAN_CONV_WALK") && atoi(getenv("IGAN_CONV_WALK")) == 0);     // A/B switch
-    const bool wt = p->w_transposed != 0;
-    const bool vecA = (p->Cin % 4 == 0) && (((uintptr_t)p->x & 15) == 0);
-    const bool vecS = (p->Cin % 4 == 0) && (((uintptr_t)p->in_scale & 15) == 0);
-    const bool vecB = ((wt ? p->Cin : p->Cout) % 4 == 0) && (((uintptr_t)p->w & 15) == 0);
-    return walk && vecA && vecB && (p->in_scale == nullptr || vecS) && (p->Cin % BK == 0);
+// A/B switch: IGAN_XCD_REMAP=0 keeps the plain block order
+bool xcd_remap_on() {
+    static const bool remap = !(getenv("IGAN_XCD_REMAP") && atoi(getenv("IGAN_XCD_REMAP")) == 0);
+    return remap;
 }
 
 // The bf16-piece form is the DEFAULT for the shapes below (round 4); IGAN_CONV_PLANES=0 runs every convolution on the fp32 instruction.
@@ -3140,8 +2983,8 @@ void launch_col_image(hipStream_t stream, const float* x, const float* scale, un
         hipLaunchKernelGGL(cols_finalize_kernel, dim3(igan::ceil_div(C, 8)), dim3(256), 0, stream, colmax + 4, inv, sc, 0, C, colmax);
     hipLaunchKernelGGL(cols_f16_kernel, dim3(igan::ceil_div(total, 256)), dim3(256), 0, stream, x, scale, out, (const float*)sc, total, cpp, C, HW);
 }
-// A/B switches inside the fp16 form's forward / data-gradient tile: IGAN_F16_TAP_OUTER=0 the slice-outermost reduction, IGAN_F16_W4=0 the eight-wave tile
-bool f16_tap_outer() { static const int v = getenv("IGAN_F16_TAP_OUTER") ? atoi(getenv("IGAN_F16_TAP_OUTER")) : 1; return v != 0; }
+// A/B switch inside the fp16 form's forward / data-gradient tile: IGAN_F16_W4=0 takes the eight-wave tile (conv_fwd_planes_kernel<2, true>: same products and
+// folds per output element, the bit-for-bit witness of the four-wave tile in tests/test_gpu_planes_variant.py)
 bool f16_w4() { static const int v = getenv("IGAN_F16_W4") ? atoi(getenv("IGAN_F16_W4")) : 1; return v != 0; }
 void launch_filter_image(hipStream_t stream, const float* w, unsigned short* wp, bool wt, int taps, int KW_, int Nn, int K) {
     const int wtotal = taps * Nn * (K / PK);
@@ -3180,24 +3023,10 @@ bool planes_shape_ok(const igan_conv2d_params* p, const FwdTile& t, int Mmax) {
     // fp16 form: the pixel's scale is shared by shuffles among the Cin / 16 threads of a pixel (a power of two within one wave), the kernel's scale
     // table holds nine taps, and the transposed tile stores four output channels per lane and register quad
     if (planes_mode() == 2 && (!pow2(p->Cin / PK) || p->Cin / PK > 64 || p->KH * p->KW > 9 || p->Cout % 4 != 0)) return false;
-#ifdef IGAN_DIAGNOSTIC      // bisecting by layer class (variant builds only: make variant VARIANT=diag DEFS=-DIGAN_DIAGNOSTIC)
-    {
-        static const int only_cin = getenv("IGAN_PLANES_ONLY_CIN") ? atoi(getenv("IGAN_PLANES_ONLY_CIN")) : 0;
-        static const int no_act = getenv("IGAN_PLANES_NO_ACT") ? atoi(getenv("IGAN_PLANES_NO_ACT")) : 0;            // 1: not with a fused epilogue; 2: only with one
-        static const int no_scale = getenv("IGAN_PLANES_NO_SCALE") ? atoi(getenv("IGAN_PLANES_NO_SCALE")) : 0;      // 1: not modulated; 2: only modulated
-        static const int kind = getenv("IGAN_PLANES_KIND") ? atoi(getenv("IGAN_PLANES_KIND")) : 0;                  // 1: stride 1 / up 1 only; 2: stride 2 only; 3: up 2 only
-        static const int wt = getenv("IGAN_PLANES_WT") ? atoi(getenv("IGAN_PLANES_WT")) : 0;                        // 1: forward calls only; 2: data gradients only
-        if (only_cin && p->Cin != only_cin) return false;
-        if ((no_act == 1 && p->act != 0) || (no_act == 2 && p->act == 0)) return false;
-        if ((no_scale == 1 && p->in_scale != nullptr) || (no_scale == 2 && p->in_scale == nullptr)) return false;
-        if ((kind == 1 && (p->stride != 1 || p->up != 1)) || (kind == 2 && p->stride != 2) || (kind == 3 && p->up != 2)) return false;
-        if ((wt == 1 && p->w_transposed) || (wt == 2 && !p->w_transposed)) return false;
-    }
-#endif
     return true;
 }
-bool use_planes_kernel(const igan_conv2d_params* p, const FwdTile& t, int Mmax) {
-    if (!planes_shape_ok(p, t, Mmax) || (((uintptr_t)p->x | (uintptr_t)p->w | (uintptr_t)p->in_scale | (uintptr_t)p->x_pieces) & 15) != 0) return false;
+bool planes_operands_aligned(const igan_conv2d_params* p) {
+    if ((((uintptr_t)p->x | (uintptr_t)p->w | (uintptr_t)p->in_scale | (uintptr_t)p->x_pieces) & 15) != 0) return false;
     if (planes_mode() == 2 && (((uintptr_t)p->y | (uintptr_t)p->out_scale | (uintptr_t)p->bias) & 15) != 0) return false;      // 16 B epilogue accesses
     return true;
 }
@@ -3211,6 +3040,58 @@ size_t planes_w_floats(const igan_conv2d_params* p) {
     return (size_t)p->KH * p->KW * p->Cin * p->Cout * 6 / 4;
 }
 
+
+// ---- the forward dispatch decision: made HERE and nowhere else ---------------------
+// igan_conv2d_plan() sizes the workspace by it, igan_conv2d_kernel_name() formats it, igan_conv2d() switches on it.
+enum FwdFamily {
+    FWD_DENSE_SMALL,    // dense_small.hip
+    FWD_THIN,           // thin_conv.hip
+    FWD_PIECES_W4,      // fp16 pieces, four-wave tile: conv_fwd_planes_w4_kernel
+    FWD_PIECES_W8,      // fp16 pieces, eight-wave tile: conv_fwd_planes_kernel<2, true>
+    FWD_PIECES_BF16,    // bf16 pieces: conv_fwd_planes_kernel<3>
+    FWD_DMA,            // fp32, LDS-DMA form of the 128x128 tile: conv_fwd_dma_kernel<wt, sc>
+    FWD_TILE            // fp32, register-staged tile: conv_fwd_kernel<BM, BN, wm, wn, wt, vec, sc>
+};
+struct FwdChoice {
+    FwdFamily family;           // what a caller who passes the planned workspace gets
+    FwdFamily fp32_family;      // FWD_DMA or FWD_TILE: what a piece-form call falls back to when its workspace cannot hold the piece images
+    int thin_kind;              // FWD_THIN: igan::thin_conv_kind()
+    int Mmax, chunks_max, nclass;
+    FwdTile t;
+    int wm, wn;                 // FWD_TILE: waves along m / n
+    bool wt, sc;                // transposed filter; an in_scale operand exists
+    bool vecA, vecB, vecS;      // 16 B paths usable for x rows / w rows / in_scale rows
+    bool vec, walk;             // all 16 B paths usable; and Cin % 32 == 0 (the walking address computation)
+    bool piece_room;            // the plan reserves room for the piece images (shapes only: plans are cached per shape)
+};
+bool is_piece_family(FwdFamily f) { return f == FWD_PIECES_W4 || f == FWD_PIECES_W8 || f == FWD_PIECES_BF16; }
+
+FwdChoice choose_fwd(const igan_conv2d_params* p) {
+    FwdChoice c = {};
+    if (is_small_dense(p)) { c.family = c.fp32_family = FWD_DENSE_SMALL; return c; }
+    if (const int kind = igan::thin_conv_kind(p)) { c.family = c.fp32_family = FWD_THIN; c.thin_kind = kind; return c; }
+    fwd_counts(p, c.Mmax, c.chunks_max, c.nclass);
+    c.t = pick_fwd_tile(c.Mmax, p->Cout);
+    c.wt = p->w_transposed != 0;
+    c.sc = p->in_scale != nullptr;
+    c.vecA = (p->Cin % 4 == 0) && (((uintptr_t)p->x & 15) == 0);
+    c.vecS = (p->Cin % 4 == 0) && (((uintptr_t)p->in_scale & 15) == 0);
+    c.vecB = ((c.wt ? p->Cin : p->Cout) % 4 == 0) && (((uintptr_t)p->w & 15) == 0);
+    c.vec = c.vecA && c.vecB && (!c.sc || c.vecS);
+    c.walk = c.vec && (p->Cin % BK == 0);
+    c.wm = 2; c.wn = 4;                                                     // 128 x 128
+    if (c.t.BM == 128 && c.t.BN == 64) { c.wm = 4; c.wn = 2; }
+    if (c.t.BM == 128 && c.t.BN == 32) { c.wm = 4; c.wn = 1; }
+    if (c.t.BM == 32) { c.wm = 1; c.wn = 4; }
+    c.fp32_family = use_dma_kernel(p, c.t, c.walk) ? FWD_DMA : FWD_TILE;
+    c.piece_room = planes_shape_ok(p, c.t, c.Mmax);
+    if (c.piece_room && planes_operands_aligned(p)) c.family = (planes_mode() != 2) ? FWD_PIECES_BF16 : (f16_w4() ? FWD_PIECES_W4 : FWD_PIECES_W8);
+    else c.family = c.fp32_family;
+    return c;
+}
+
+// The weight gradient's decision follows its helpers, further down (choose_wgrad).
+
 }  // namespace
 
 // Diagnostic hook (tools/conv_phases.py): when set, every forward-type launch writes 4 time stamps per workgroup (entry, main
@@ -3218,7 +3099,7 @@ size_t planes_w_floats(const igan_conv2d_params* p) {
 static unsigned long long* g_conv_diag = nullptr;
 extern "C" void igan_debug_set_conv_diag(unsigned long long* p) { g_conv_diag = p; }
 
-static int conv2d_plan_tiles(const igan_conv2d_params* p, int* splits, int* sliced_tiles, size_t* workspace_floats);
+static int conv2d_plan_tiles(const igan_conv2d_params* p, const FwdChoice& c, int* splits, int* sliced_tiles, size_t* workspace_floats);
 
 extern "C" int igan_conv2d_plan(const igan_conv2d_params* p, int* splits, int* sliced_tiles, size_t* workspace_floats) {
     IGAN_REQUIRE(p && splits && sliced_tiles && workspace_floats, "conv2d_plan: null argument");
@@ -3226,29 +3107,19 @@ extern "C" int igan_conv2d_plan(const igan_conv2d_params* p, int* splits, int* s
     *splits = 1;
     *sliced_tiles = 0;
     *workspace_floats = 0;
-    if (is_small_dense(p) || igan::thin_conv_kind(p)) return IGAN_OK;
-    if (int rc = conv2d_plan_tiles(p, splits, sliced_tiles, workspace_floats)) return rc;
-    int Mmax, chunks_max, nclass;
-    fwd_counts(p, Mmax, chunks_max, nclass);
-    if (planes_shape_ok(p, pick_fwd_tile(Mmax, p->Cout), Mmax))      // the piece images of x and of the filter follow the partial tiles
+    const FwdChoice c = choose_fwd(p);
+    if (c.family == FWD_DENSE_SMALL || c.family == FWD_THIN) return IGAN_OK;
+    if (int rc = conv2d_plan_tiles(p, c, splits, sliced_tiles, workspace_floats)) return rc;
+    if (c.piece_room)      // the piece images of x and of the filter follow the partial tiles
         *workspace_floats += planes_x_floats(p) + planes_w_floats(p);
     return IGAN_OK;
 }
 
-static int conv2d_plan_tiles(const igan_conv2d_params* p, int* splits, int* sliced_tiles, size_t* workspace_floats) {
-    int Mmax, chunks_max, nclass;
-    fwd_counts(p, Mmax, chunks_max, nclass);
-    const FwdTile t = pick_fwd_tile(Mmax, p->Cout);
-    const TileList l = tile_list(p, t, Mmax, nclass);
-    {   // whole rounds: nothing to slice -- unless the CUs end on an unpaired tile (odd tiles per CU) and the A/B switch
-        // IGAN_SLICE_ODD=1 asks for that round to be cut in two (both workgroup slots of a CU stay busy to the end)
-        static const bool odd = getenv("IGAN_SLICE_ODD") && atoi(getenv("IGAN_SLICE_ODD")) == 1;
-        if (l.rem == 0 && !(odd && (l.T / device_cus()) % 2 == 1)) return IGAN_OK;
-    }
-    {   // A/B switch: IGAN_SLICE_BIG=0 leaves layers with at least one whole round unsliced
-        static const bool big = !(getenv("IGAN_SLICE_BIG") && atoi(getenv("IGAN_SLICE_BIG")) == 0);
-        if (!big && l.T >= device_cus()) return IGAN_OK;
-    }
+static int conv2d_plan_tiles(const igan_conv2d_params* p, const FwdChoice& c, int* splits, int* sliced_tiles, size_t* workspace_floats) {
+    const int chunks_max = c.chunks_max;
+    const FwdTile t = c.t;
+    const TileList l = tile_list(p, t, c.Mmax, c.nclass);
+    if (l.rem == 0) return IGAN_OK;     // whole rounds: nothing to slice
     // Which trailing tiles to slice, and how finely, by a small cost model (measured on the 128x128 tile):
     // two co-resident workgroups finish a chunk each in 4.4 us, a lone one in 3.3 us (the matrix pipe is
     // per SIMD, so a pair is only 1.5x as efficient as a single).  A CU that holds n blocks of a tile's
@@ -3281,42 +3152,25 @@ static int conv2d_plan_tiles(const igan_conv2d_params* p, int* splits, int* slic
     return IGAN_OK;
 }
 
-// Which instantiation igan_conv2d() launches for these parameters (host-only; for profiling tools:
-// the string equals the kernel name rocprofv3 reports, up to the anonymous namespace prefix).
+// Which instantiation igan_conv2d() launches for these parameters when the caller passes the planned workspace (host-only; for
+// profiling tools: the string equals the kernel name rocprofv3 reports, up to the anonymous namespace prefix).
 extern "C" int igan_conv2d_kernel_name(const igan_conv2d_params* p, char* buf, int buflen) {
     IGAN_REQUIRE(p && buf && buflen > 0, "conv2d_kernel_name: null argument");
     if (int rc = fwd_geometry_check(p)) return rc;
-    if (is_small_dense(p)) {
-        snprintf(buf, (size_t)buflen, "dense_small_kernel<%d, %s>", igan::dense_small_rows(p->N), p->w_transposed ? "true" : "false");
-        return IGAN_OK;
+    const FwdChoice c = choose_fwd(p);
+    const char* wt = c.wt ? "true" : "false";
+    const char* sc = c.sc ? "true" : "false";
+    switch (c.family) {
+    case FWD_DENSE_SMALL: snprintf(buf, (size_t)buflen, "dense_small_kernel<%d, %s>", igan::dense_small_rows(p->N), p->w_transposed ? "true" : "false"); break;
+    case FWD_THIN: snprintf(buf, (size_t)buflen, "%s<%d>", c.thin_kind == 1 ? "thin_out_kernel" : "thin_in_kernel", p->KH * p->KW); break;
+    case FWD_PIECES_W4: snprintf(buf, (size_t)buflen, "conv_fwd_planes_w4_kernel"); break;
+    case FWD_PIECES_W8:
+    case FWD_PIECES_BF16: snprintf(buf, (size_t)buflen, "conv_fwd_planes_kernel"); break;
+    case FWD_DMA: snprintf(buf, (size_t)buflen, "conv_fwd_dma_kernel<%s, %s>", wt, sc); break;
+    case FWD_TILE:
+        snprintf(buf, (size_t)buflen, "conv_fwd_kernel<%d, %d, %d, %d, %s, %s, %s>", c.t.BM, c.t.BN, c.wm, c.wn, wt, c.vec ? "true" : "false", sc);
+        break;
     }
-    if (const int kind = igan::thin_conv_kind(p)) {
-        snprintf(buf, (size_t)buflen, "%s<%d>", kind == 1 ? "thin_out_kernel" : "thin_in_kernel", p->KH * p->KW);
-        return IGAN_OK;
-    }
-    int Mmax, chunks_max, nclass;
-    fwd_counts(p, Mmax, chunks_max, nclass);
-    const FwdTile t = pick_fwd_tile(Mmax, p->Cout);
-    const bool wt = p->w_transposed != 0;
-    const bool vecA = (p->Cin % 4 == 0) && (((uintptr_t)p->x & 15) == 0);
-    const bool vecS = (p->Cin % 4 == 0) && (((uintptr_t)p->in_scale & 15) == 0);
-    const bool vecB = ((wt ? p->Cin : p->Cout) % 4 == 0) && (((uintptr_t)p->w & 15) == 0);
-    const bool vec = vecA && vecB && (p->in_scale == nullptr || vecS);
-    if (use_planes_kernel(p, t, Mmax)) {
-        snprintf(buf, (size_t)buflen, (planes_mode() == 2 && f16_tap_outer() && f16_w4()) ? "conv_fwd_planes_w4_kernel" : "conv_fwd_planes_kernel");
-        return IGAN_OK;
-    }
-    if (use_dma_kernel(p, t, walk_ok(p))) {
-        snprintf(buf, (size_t)buflen, "conv_fwd_dma_kernel<%s, %s>", wt ? "true" : "false", p->in_scale ? "true" : "false");
-        return IGAN_OK;
-    }
-    int wm = 2, wn = 2;
-    if (t.BM == 128 && t.BN == 128 && eight_waves("IGAN_CONV_8WAVE")) wn = 4;
-    if (t.BM == 128 && t.BN == 64 && eight_waves("IGAN_CONV_8WAVE")) { wm = 4; wn = 2; }
-    if (t.BM == 128 && t.BN == 32) { wm = 4; wn = 1; }
-    if (t.BM == 32) { wm = 1; wn = 4; }
-    snprintf(buf, (size_t)buflen, "conv_fwd_kernel<%d, %d, %d, %d, %s, %s, %s>", t.BM, t.BN, wm, wn, wt ? "true" : "false",
-             vec ? "true" : "false", p->in_scale ? "true" : "false");
     return IGAN_OK;
 }
 
@@ -3330,31 +3184,33 @@ extern "C" int igan_conv2d(igan_stream_t stream_, const igan_conv2d_params* p) {
         IGAN_REQUIRE((((uintptr_t)p->x_colmax | (uintptr_t)p->x | (uintptr_t)p->in_scale) & 15) == 0, "conv2d: x_colmax, x and in_scale must be 16-byte aligned");
     }
     auto colmax_own_pass = [&]() { if (p->x_colmax) launch_colmax_only(stream, p->x, p->in_scale, p->x_colmax, p->N * p->H * p->W, p->H * p->W, p->Cin); };
-    if (is_small_dense(p)) {
+    const FwdChoice c = choose_fwd(p);
+    if (c.family == FWD_DENSE_SMALL) {
         colmax_own_pass();
         IGAN_REQUIRE(p->noise == nullptr, "conv2d: the fused noise epilogue is not offered on the small dense path");
         dense_small(stream, p->x, p->w, p->y, p->N, p->Cin, p->Cout, p->w_transposed != 0, p->alpha);
         IGAN_LAUNCH_CHECK("conv2d dense launch");
         return IGAN_OK;
     }
-    if (const int kind = thin_conv_kind(p)) {
+    if (c.family == FWD_THIN) {
         colmax_own_pass();
         IGAN_REQUIRE(p->noise == nullptr, "conv2d: the fused noise epilogue is not offered on the thin-channel path");
-        thin_conv(stream, p, kind);
+        thin_conv(stream, p, c.thin_kind);
         IGAN_LAUNCH_CHECK("conv2d thin-channel launch");
         return IGAN_OK;
     }
-    int Mmax, chunks_max, nclass;
-    fwd_counts(p, Mmax, chunks_max, nclass);
-    const FwdTile t = pick_fwd_tile(Mmax, p->Cout);
-    const TileList l = tile_list(p, t, Mmax, nclass);
+    const FwdTile t = c.t;
+    const TileList l = tile_list(p, t, c.Mmax, c.nclass);
     int splits = std::max(1, p->splits);
     const int sliced = std::min(std::max(p->sliced_tiles, 0), l.T);   // trailing tiles cut along the reduction axis
     if (sliced == 0) splits = 1;
     const size_t partial_floats = (splits > 1) ? (size_t)sliced * splits * t.BM * t.BN : 0;
-    // the variant needs its piece images' room behind the partial tiles; a caller that did not provide it gets the fp32 kernel
-    const bool planes = use_planes_kernel(p, t, Mmax) && p->workspace != nullptr &&
-                        p->workspace_floats >= partial_floats + planes_x_floats(p) + planes_w_floats(p);
+    // The one thing the launch decides beyond choose_fwd(): the piece form needs its images' room behind the partial tiles, and a
+    // caller that did not provide it gets the fp32 family.
+    FwdFamily family = c.family;
+    if (is_piece_family(family) && !(p->workspace != nullptr && p->workspace_floats >= partial_floats + planes_x_floats(p) + planes_w_floats(p)))
+        family = c.fp32_family;
+    const bool planes = is_piece_family(family);
     if (splits > 1) {
         IGAN_REQUIRE(p->workspace != nullptr, "conv2d: splits > 1 needs a workspace");
         IGAN_REQUIRE(p->workspace_floats >= partial_floats, "conv2d: workspace too small");
@@ -3376,48 +3232,30 @@ extern "C" int igan_conv2d(igan_stream_t stream_, const igan_conv2d_params* p) {
     a.full_tiles = (splits > 1) ? l.T - sliced : l.T;
     a.cpt = ceil_div(p->Cin, BK);
     a.Mtot = p->N * p->OH * p->OW;
-    a.vecA = (p->Cin % 4 == 0) && (((uintptr_t)p->x & 15) == 0);
-    a.vecS = (p->Cin % 4 == 0) && (((uintptr_t)p->in_scale & 15) == 0);
-    if (p->w_transposed) a.vecB = (p->Cin % 4 == 0) && (((uintptr_t)p->w & 15) == 0);
-    else a.vecB = (p->Cout % 4 == 0) && (((uintptr_t)p->w & 15) == 0);
+    a.vecA = c.vecA; a.vecB = c.vecB; a.vecS = c.vecS;
     a.vecY = (p->Cout % 2 == 0) && ((((uintptr_t)p->y | (uintptr_t)p->out_scale) & 7) == 0);
     a.alpha = p->alpha;
-    {   // A/B switch: IGAN_XCD_REMAP=0 keeps the plain block order
-        static const bool remap = !(getenv("IGAN_XCD_REMAP") && atoi(getenv("IGAN_XCD_REMAP")) == 0);
-        a.xcd_remap = remap ? 1 : 0;
-        static const bool walk = !(getenv("IGAN_CONV_WALK") && atoi(getenv("IGAN_CONV_WALK")) == 0);     // A/B switch
-        a.diag = g_conv_diag;
-        static const int stagger = getenv("IGAN_CONV_STAGGER") ? atoi(getenv("IGAN_CONV_STAGGER")) : 0;     // experiment
-        a.stagger = stagger;
-        static const bool bscale = !(getenv("IGAN_CONV_BSCALE") && atoi(getenv("IGAN_CONV_BSCALE")) == 0);     // A/B switch
-        a.b_scale = bscale ? 1 : 0;
-        static const bool pprio = !(getenv("IGAN_CONV_PROLOGUE_PRIO") && atoi(getenv("IGAN_CONV_PROLOGUE_PRIO")) == 0);     // A/B switch
-        a.prio = pprio ? 1 : 0;
-        a.walk = (walk && a.vecA && a.vecB && (a.in_scale == nullptr || a.vecS) && (p->Cin % BK == 0)) ? 1 : 0;
-    }
+    a.xcd_remap = xcd_remap_on() ? 1 : 0;
+    a.walk = c.walk ? 1 : 0;
+    a.diag = g_conv_diag;
+    a.stagger = 0;      // today's default of the removed switch IGAN_CONV_STAGGER
+    a.b_scale = 1;      // today's default of the removed switch IGAN_CONV_BSCALE
+    a.prio = 1;         // today's default of the removed switch IGAN_CONV_PROLOGUE_PRIO
+    a.diag_mode = 0;    // today's default of the removed switch IGAN_DIAG_MODE
     a.bias = p->bias; a.act = p->act; a.act_alpha = p->act_alpha; a.act_gain = p->act_gain;
     a.noise = p->act ? p->noise : nullptr; a.noise_strength = p->noise_strength; a.noise_bcast = p->noise_bcast;
     a.xp = nullptr; a.wp = nullptr;
-    a.diag_mode = 0;
-#ifdef IGAN_DIAGNOSTIC
-    a.diag_mode = getenv("IGAN_DIAG_MODE") ? atoi(getenv("IGAN_DIAG_MODE")) : 0;
-#endif
 
     dim3 grid(a.full_tiles + (l.T - a.full_tiles) * splits);
-    const bool wt = p->w_transposed != 0;
-    const bool vec = a.vecA && a.vecB && (a.in_scale == nullptr || a.vecS);
-    bool launched = false;
     if (!planes) colmax_own_pass();
     if (planes) {       // piece form: write the two piece images, then the tile kernel
         IGAN_REQUIRE(p->x_pieces == nullptr || planes_mode() == 1, "conv2d: the two-piece fp16 form writes its own images (one scale per pixel here, per channel in the weight gradient): x_pieces must be NULL");
         IGAN_REQUIRE(p->x_pieces == nullptr || p->x_pieces_bytes == planes_x_floats(p) * 4, "conv2d: x_pieces is not the image of this x (x_pieces_bytes != N*H*W*Cin*6)");
         const unsigned short* xp = reinterpret_cast<const unsigned short*>(p->x_pieces);
         unsigned short* wp = reinterpret_cast<unsigned short*>(p->workspace + partial_floats + planes_x_floats(p));
-        const int cpp = p->Cin / PK;
         if (xp == nullptr) {         // no image from the caller: write it behind the partial tiles
             unsigned short* own = reinterpret_cast<unsigned short*>(p->workspace + partial_floats);
-            if (a.diag_mode & 1) {}      // DIAGNOSTIC: stale image
-            else if (planes_mode() == 2) launch_row_image(stream, p->x, p->in_scale, own, p->N * p->H * p->W, p->H * p->W, p->Cin, p->x_colmax);
+            if (planes_mode() == 2) launch_row_image(stream, p->x, p->in_scale, own, p->N * p->H * p->W, p->H * p->W, p->Cin, p->x_colmax);
             else launch_piece_image(stream, p->x, p->in_scale, own, p->N * p->H * p->W, p->H * p->W, p->Cin);
             xp = own;
         }
@@ -3427,42 +3265,40 @@ extern "C" int igan_conv2d(igan_stream_t stream_, const igan_conv2d_params* p) {
             IGAN_REQUIRE(p->w_pieces_bytes == igan_filter_image_bytes(p->KH, p->KW, p->Cin, p->Cout) && (((uintptr_t)p->w_pieces) & 15) == 0,
                          "conv2d: w_pieces is not an image igan_filter_image() wrote for this filter (size / alignment)");
             wp = reinterpret_cast<unsigned short*>(const_cast<void*>(p->w_pieces));
-        } else if (!(a.diag_mode & 1)) launch_filter_image(stream, p->w, wp, wt, p->KH * p->KW, p->KW, p->Cout, p->Cin);
+        } else launch_filter_image(stream, p->w, wp, c.wt, p->KH * p->KW, p->KW, p->Cout, p->Cin);
         a.xp = xp; a.wp = wp;
-        a.cpt = cpp;
-        if (a.diag_mode & 2) {}          // DIAGNOSTIC: image kernels only
-        else if (planes_mode() == 2) {
-            // reduction order of the fp16 form (see the kernel): tap outermost (the cross terms are folded once per tap); A/B switch IGAN_F16_TAP_OUTER=0:
-            // slice outermost, every step folds its cross terms.  Measured (profiles/r05_f16_rowscale.txt): kernel 490.6 -> 457.2 us on G 128 Conv1
-            // (Cin 128), 451.4 -> 428.0 us on G 32 Conv1 (Cin 512); whole layer list forward 186.0 -> 194.4, data gradient 189.2 -> 198.0 TFLOP/s.
-            const bool tapo = f16_tap_outer();
-            if (tapo && f16_w4()) hipLaunchKernelGGL(conv_fwd_planes_w4_kernel, grid, dim3(256), 0, stream, a);       // the four-wave tile (fragments of the next chunk prefetched into registers): whole calls 4-5 % shorter, bench +1.1 % (profiles/r05_w4_tile.txt)
-            else if (tapo) hipLaunchKernelGGL((conv_fwd_planes_kernel<2, true>), grid, dim3(512), 0, stream, a);
-            else hipLaunchKernelGGL((conv_fwd_planes_kernel<2, false>), grid, dim3(512), 0, stream, a);
-        } else hipLaunchKernelGGL((conv_fwd_planes_kernel<3>), grid, dim3(512), 0, stream, a);
+        a.cpt = p->Cin / PK;
+    }
+    switch (family) {
+    case FWD_PIECES_W4:     // the four-wave tile (fragments of the next chunk prefetched into registers): whole calls 4-5 % shorter, bench +1.1 % (profiles/r05_w4_tile.txt)
+        hipLaunchKernelGGL(conv_fwd_planes_w4_kernel, grid, dim3(256), 0, stream, a);
         IGAN_LAUNCH_CHECK("conv2d (piece form) launch");
-        launched = true;
-    } else
-    if (use_dma_kernel(p, t, a.walk != 0)) {       // LDS-DMA form of the 128x128 tile
-        // (the in-register bf16 split forms of round 2 -- IGAN_CONV_BF16X3, PIECES = 2 / 3 of this kernel -- are no longer instantiated: measure-only, superseded by the
-        // piece kernels, and the only kernels of the library beside the 16-wave experiment that spilled to scratch: tools/asm_scan.py, HISTORY.md section 8)
-        if (wt) {
-            if (a.in_scale) hipLaunchKernelGGL((conv_fwd_dma_kernel<true, true>), grid, dim3(512), 0, stream, a);
+        break;
+    case FWD_PIECES_W8:
+        hipLaunchKernelGGL((conv_fwd_planes_kernel<2, true>), grid, dim3(512), 0, stream, a);
+        IGAN_LAUNCH_CHECK("conv2d (piece form) launch");
+        break;
+    case FWD_PIECES_BF16:
+        hipLaunchKernelGGL((conv_fwd_planes_kernel<3>), grid, dim3(512), 0, stream, a);
+        IGAN_LAUNCH_CHECK("conv2d (piece form) launch");
+        break;
+    case FWD_DMA:           // LDS-DMA form of the 128x128 tile
+        if (c.wt) {
+            if (c.sc) hipLaunchKernelGGL((conv_fwd_dma_kernel<true, true>), grid, dim3(512), 0, stream, a);
             else hipLaunchKernelGGL((conv_fwd_dma_kernel<true, false>), grid, dim3(512), 0, stream, a);
         } else {
-            if (a.in_scale) hipLaunchKernelGGL((conv_fwd_dma_kernel<false, true>), grid, dim3(512), 0, stream, a);
+            if (c.sc) hipLaunchKernelGGL((conv_fwd_dma_kernel<false, true>), grid, dim3(512), 0, stream, a);
             else hipLaunchKernelGGL((conv_fwd_dma_kernel<false, false>), grid, dim3(512), 0, stream, a);
         }
         IGAN_LAUNCH_CHECK("conv2d (LDS-DMA) launch");
-        launched = true;
+        break;
+    default:                // FWD_TILE: the (wm, wn) of choose_fwd(), spelled as template arguments
+        if (t.BM == 128 && t.BN == 128) launch_fwd<128, 128, 2, 4>(stream, a, grid, c.wt, c.vec);
+        else if (t.BM == 128 && t.BN == 64) launch_fwd<128, 64, 4, 2>(stream, a, grid, c.wt, c.vec);
+        else if (t.BM == 128 && t.BN == 32) launch_fwd<128, 32, 4, 1>(stream, a, grid, c.wt, c.vec);
+        else launch_fwd<32, 128, 1, 4>(stream, a, grid, c.wt, c.vec);
+        break;
     }
-    if (launched) {}
-    else if (t.BM == 128 && t.BN == 128 && eight_waves("IGAN_CONV_8WAVE")) launch_fwd<128, 128, 2, 4>(stream, a, grid, wt, vec);
-    else if (t.BM == 128 && t.BN == 128) launch_fwd<128, 128, 2, 2>(stream, a, grid, wt, vec);
-    else if (t.BM == 128 && t.BN == 64 && eight_waves("IGAN_CONV_8WAVE")) launch_fwd<128, 64, 4, 2>(stream, a, grid, wt, vec);
-    else if (t.BM == 128 && t.BN == 64) launch_fwd<128, 64, 2, 2>(stream, a, grid, wt, vec);
-    else if (t.BM == 128 && t.BN == 32) launch_fwd<128, 32, 4, 1>(stream, a, grid, wt, vec);
-    else launch_fwd<32, 128, 1, 4>(stream, a, grid, wt, vec);
     IGAN_LAUNCH_CHECK("conv2d launch");
 
     if (splits > 1) {
@@ -3515,12 +3351,11 @@ WgTile pick_wg_tile(int Cin, int Cout) {
     return t;
 }
 
-int wgrad_splits(const igan_conv2d_wgrad_params* p) {
+int wgrad_splits(const igan_conv2d_wgrad_params* p, const WgTile& t) {
     // One block per (tap, Cin tile, Cout tile, pixel slice).  The kernel runs 2 workgroups per CU
     // (LDS / VGPR), i.e. 512 co-resident workgroups on 256 CUs: size the grid to whole rounds of 512
     // so that no round runs half empty (a 774-block grid ran 1.5 rounds: 25 % of the machine idle
     // for a third of the time).
-    const WgTile t = pick_wg_tile(p->Cin, p->Cout);
     const long long tiles = (long long)igan::ceil_div(p->Cin, t.BM) * igan::ceil_div(p->Cout, t.BN) * p->KH * p->KW;
     const int up = p->up;
     const long long kpix = (long long)p->N * ((p->OH + up - 1) / up) * ((p->OW + up - 1) / up);
@@ -3547,17 +3382,6 @@ int wgrad_min_rows() {
 bool wgrad_planes_shape_ok(const igan_conv2d_wgrad_params* p) {
     static const bool wg = !(getenv("IGAN_WGRAD_PLANES") && atoi(getenv("IGAN_WGRAD_PLANES")) == 0);      // A/B switch inside the piece form
     if (!planes_enabled() || !wg || p->KH * p->KW == 1 || p->Cin < 128 || p->Cout < 128 || p->Cin % 32 != 0 || p->Cout % 32 != 0) return false;
-#ifdef IGAN_DIAGNOSTIC
-    {   // DIAGNOSTIC ONLY (bisecting by layer class): IGAN_WGRAD_PLANES_CIN=<n> keeps the piece form for weight gradients with Cin == n only,
-        // IGAN_WGRAD_PLANES_KIND=plain|stride|up for stride 1 without up-sampling / stride 2 / up 2 only
-        static const int only_cin = getenv("IGAN_WGRAD_PLANES_CIN") ? atoi(getenv("IGAN_WGRAD_PLANES_CIN")) : 0;
-        static const char* kind = getenv("IGAN_WGRAD_PLANES_KIND");
-        if (only_cin && p->Cin != only_cin) return false;
-        if (kind && kind[0] == 'p' && (p->stride != 1 || p->up != 1)) return false;
-        if (kind && kind[0] == 's' && p->stride != 2) return false;
-        if (kind && kind[0] == 'u' && p->up != 2) return false;
-    }
-#endif
     if ((long long)p->N * p->OH * p->OW < wgrad_min_rows() * (long long)p->up * p->up) return false;
     if ((long long)p->N * p->H * p->W * p->Cin * 6 >= 0x7FFFFF00LL || (long long)p->N * p->OH * p->OW * p->Cout * 6 >= 0x7FFFFF00LL) return false;
     // fp16 form: the column-maximum pass gives every thread one channel quad (C / 4 a power of two <= 256)
@@ -3573,35 +3397,81 @@ size_t wgrad_planes_dy_floats(const igan_conv2d_wgrad_params* p) {
     return (size_t)p->N * p->OH * p->OW * p->Cout * 6 / 4;
 }
 
+// ---- the weight gradient's dispatch decision: made HERE and nowhere else -----------
+// igan_conv2d_wgrad_plan() sizes the workspace by it, igan_conv2d_wgrad_kernel_name() formats it, igan_conv2d_wgrad() switches on it.
+enum WgradFamily {
+    WG_DENSE_SMALL,     // dense_small.hip
+    WG_THIN,            // thin_conv.hip
+    WG_PIECES,          // conv_wgrad_planes_kernel<2> (fp16 pieces) or <3> (bf16 pieces), by planes_mode()
+    WG_TILE             // fp32: conv_wgrad_kernel<BM, BN, wm, wn, vec, scm>
+};
+struct WgradChoice {
+    WgradFamily family;         // what a caller who passes the planned workspace gets
+    WgradFamily tile_family;    // WG_PIECES or WG_TILE: what a thin-channel call falls back to when its workspace cannot hold the pixel blocks
+    int thin_kind;              // WG_THIN: igan::thin_wgrad_kind()
+    WgTile t;
+    int wm, wn;                 // WG_TILE: waves along ci / co
+    bool vecA, vecB, vecSA, vecSB, vec;     // 16 B paths usable for x / dy / in_scale / out_scale rows; all of those that exist
+    int scm;                    // scale mode of conv_wgrad_kernel: 0 neither scale, 1 both, 2 exactly one
+    bool piece_room;            // the plan reserves room for the piece images (shapes only)
+};
+
+WgradChoice choose_wgrad(const igan_conv2d_wgrad_params* p) {
+    WgradChoice c = {};
+    if (is_small_dense_wgrad(p)) { c.family = c.tile_family = WG_DENSE_SMALL; return c; }
+    c.t = pick_wg_tile(p->Cin, p->Cout);
+    c.vecA = (p->Cin % 4 == 0) && (((uintptr_t)p->x & 15) == 0);
+    c.vecB = (p->Cout % 4 == 0) && (((uintptr_t)p->dy & 15) == 0);
+    c.vecSA = (p->Cin % 4 == 0) && (((uintptr_t)p->in_scale & 15) == 0);
+    c.vecSB = (p->Cout % 4 == 0) && (((uintptr_t)p->out_scale & 15) == 0);
+    c.vec = c.vecA && c.vecB && (p->in_scale == nullptr || c.vecSA) && (p->out_scale == nullptr || c.vecSB);
+    c.scm = (p->in_scale && p->out_scale) ? 1 : ((p->in_scale || p->out_scale) ? 2 : 0);
+    // 8 waves pay on the short pixel axes (32x32 and below: +1.5 %), 4 waves on the 128x128 layers (+3-4 %): measured, tools/conv_bench.py
+    const bool long_axis = (long long)p->OH * p->OW >= 128LL * 128LL;
+    // (round 6) the scaled forms (scm != 0: the modulated layers below the piece form's row threshold) take the four-wave tile: at the 128 registers of eight waves they
+    // spill ten registers to scratch inside the loop (tools/asm_scan.py), at 256 they do not
+    c.wm = 2; c.wn = (!long_axis && c.scm == 0) ? 4 : 2;                   // 128 x 128
+    if (c.t.BM == 128 && c.t.BN == 32) { c.wm = 4; c.wn = 1; }
+    if (c.t.BM == 32) { c.wm = 1; c.wn = 4; }
+    c.piece_room = wgrad_planes_shape_ok(p);
+    const bool aligned = (((uintptr_t)p->x | (uintptr_t)p->dy | (uintptr_t)p->in_scale | (uintptr_t)p->out_scale | (uintptr_t)p->x_pieces | (uintptr_t)p->dy_pieces) & 15) == 0;
+    c.tile_family = (c.piece_room && aligned) ? WG_PIECES : WG_TILE;
+    c.thin_kind = igan::thin_wgrad_kind(p);
+    c.family = c.thin_kind ? WG_THIN : c.tile_family;
+    return c;
+}
+
 }  // namespace
 
 extern "C" int igan_conv2d_wgrad_plan(const igan_conv2d_wgrad_params* p, int* splits, size_t* workspace_floats) {
     IGAN_REQUIRE(p && splits && workspace_floats, "conv2d_wgrad_plan: null argument");
     if (int rc = wgrad_geometry_check(p)) return rc;
-    if (is_small_dense_wgrad(p)) { *splits = 1; *workspace_floats = 0; return IGAN_OK; }
-    if (const int kind = igan::thin_wgrad_kind(p)) {
+    const WgradChoice c = choose_wgrad(p);
+    if (c.family == WG_DENSE_SMALL) { *splits = 1; *workspace_floats = 0; return IGAN_OK; }
+    if (c.family == WG_THIN) {
         *splits = 2;                           // "uses the workspace"; the pixel blocking is internal
-        *workspace_floats = igan::thin_wgrad_workspace(p, kind);
+        *workspace_floats = igan::thin_wgrad_workspace(p, c.thin_kind);
         return IGAN_OK;
     }
-    const int s = wgrad_splits(p);
+    const int s = wgrad_splits(p, c.t);
     *splits = s;
     *workspace_floats = (s > 1) ? (size_t)s * p->KH * p->KW * p->Cin * p->Cout : 0;
-    if (wgrad_planes_shape_ok(p))       // the piece images of x and dy follow the partial filters
+    if (c.piece_room)       // the piece images of x and dy follow the partial filters
         *workspace_floats += wgrad_planes_x_floats(p) + wgrad_planes_dy_floats(p);
     return IGAN_OK;
 }
 
-// Which kernel family igan_conv2d_wgrad() runs for these parameters (host-only, for the profiling tools; ABI v6).
+// Which kernel family igan_conv2d_wgrad() runs for these parameters when the caller passes the planned workspace (host-only, for the profiling tools; ABI v6).
 extern "C" int igan_conv2d_wgrad_kernel_name(const igan_conv2d_wgrad_params* p, char* buf, int buflen) {
-    using namespace igan;
     IGAN_REQUIRE(p && buf && buflen > 0, "conv2d_wgrad_kernel_name: null argument");
     if (int rc = wgrad_geometry_check(p)) return rc;
     const char* name = "conv_wgrad_kernel";
-    if (is_small_dense_wgrad(p)) name = "dense_small_wgrad_kernel";
-    else if (thin_wgrad_kind(p)) name = "thin_wgrad_kernel";
-    else if (wgrad_planes_shape_ok(p) && (((uintptr_t)p->x | (uintptr_t)p->dy | (uintptr_t)p->in_scale | (uintptr_t)p->out_scale | (uintptr_t)p->x_pieces | (uintptr_t)p->dy_pieces) & 15) == 0)
-        name = "conv_wgrad_planes_kernel";
+    switch (choose_wgrad(p).family) {
+    case WG_DENSE_SMALL: name = "dense_small_wgrad_kernel"; break;
+    case WG_THIN: name = "thin_wgrad_kernel"; break;
+    case WG_PIECES: name = "conv_wgrad_planes_kernel"; break;
+    case WG_TILE: break;
+    }
     snprintf(buf, (size_t)buflen, "%s", name);
     return IGAN_OK;
 }
@@ -3611,17 +3481,21 @@ extern "C" int igan_conv2d_wgrad(igan_stream_t stream_, const igan_conv2d_wgrad_
     hipStream_t stream = (hipStream_t)stream_;
     IGAN_REQUIRE(p != nullptr, "conv2d_wgrad: null params");
     if (int rc = wgrad_geometry_check(p)) return rc;
-    if (is_small_dense_wgrad(p)) {
+    const WgradChoice c = choose_wgrad(p);
+    if (c.family == WG_DENSE_SMALL) {
         dense_small_wgrad(stream, p->x, p->dy, p->dw, p->N, p->Cin, p->Cout, p->alpha);
         IGAN_LAUNCH_CHECK("conv2d_wgrad dense launch");
         return IGAN_OK;
     }
-    if (const int kind = thin_wgrad_kind(p)) {
-        if (p->workspace && p->workspace_floats >= thin_wgrad_workspace(p, kind) && (((uintptr_t)p->workspace) & 15) == 0) {
-            thin_wgrad(stream, p, kind);
-            IGAN_LAUNCH_CHECK("conv2d_wgrad thin-channel launch");
-            return IGAN_OK;
-        }
+    // The two things the launch decides beyond choose_wgrad(), both about the workspace the caller actually passed: the thin-channel
+    // path needs its pixel blocks' room (else the call takes the tile family), ...
+    WgradFamily family = c.family;
+    if (family == WG_THIN && !(p->workspace && p->workspace_floats >= thin_wgrad_workspace(p, c.thin_kind) && (((uintptr_t)p->workspace) & 15) == 0))
+        family = c.tile_family;
+    if (family == WG_THIN) {
+        thin_wgrad(stream, p, c.thin_kind);
+        IGAN_LAUNCH_CHECK("conv2d_wgrad thin-channel launch");
+        return IGAN_OK;
     }
     const int splits = std::max(1, p->splits);
     const size_t wsize = (size_t)p->KH * p->KW * p->Cin * p->Cout;
@@ -3641,24 +3515,20 @@ extern "C" int igan_conv2d_wgrad(igan_stream_t stream_, const igan_conv2d_wgrad_
     a.stride = p->stride; a.up_shift = (p->up == 2) ? 1 : 0;
     a.pad_y = p->pad_y; a.pad_x = p->pad_x;
     a.splits = splits;
-    a.vecA = (p->Cin % 4 == 0) && (((uintptr_t)p->x & 15) == 0);
-    a.vecB = (p->Cout % 4 == 0) && (((uintptr_t)p->dy & 15) == 0);
-    a.vecSA = (p->Cin % 4 == 0) && (((uintptr_t)p->in_scale & 15) == 0);
-    a.vecSB = (p->Cout % 4 == 0) && (((uintptr_t)p->out_scale & 15) == 0);
-
+    a.vecA = c.vecA; a.vecB = c.vecB; a.vecSA = c.vecSA; a.vecSB = c.vecSB;
     a.vecY = (p->Cout % 2 == 0) && (((uintptr_t)a.out & 7) == 0);
     a.alpha = p->alpha;
-    {
-        static const bool remap = !(getenv("IGAN_XCD_REMAP") && atoi(getenv("IGAN_XCD_REMAP")) == 0);
-        a.xcd_remap = remap ? 1 : 0;
-    }
+    a.xcd_remap = xcd_remap_on() ? 1 : 0;
 
-    const WgTile t = pick_wg_tile(p->Cin, p->Cout);
+    const WgTile t = c.t;
     dim3 grid(ceil_div(p->Cin, t.BM), ceil_div(p->Cout, t.BN), p->KH * p->KW * splits);
     a.xp = nullptr; a.dyp = nullptr;
     const size_t partial_floats = (splits > 1) ? (size_t)splits * wsize : 0;
-    if (wgrad_planes_shape_ok(p) && p->workspace != nullptr && (((uintptr_t)p->workspace | (uintptr_t)p->x | (uintptr_t)p->dy | (uintptr_t)p->in_scale | (uintptr_t)p->out_scale | (uintptr_t)p->x_pieces | (uintptr_t)p->dy_pieces) & 15) == 0 &&
-        p->workspace_floats >= partial_floats + wgrad_planes_x_floats(p) + wgrad_planes_dy_floats(p)) {
+    // ... and the piece form needs an aligned workspace with its images' room behind the partial filters (else the fp32 tile).
+    if (family == WG_PIECES && !(p->workspace != nullptr && (((uintptr_t)p->workspace) & 15) == 0 &&
+                                 p->workspace_floats >= partial_floats + wgrad_planes_x_floats(p) + wgrad_planes_dy_floats(p)))
+        family = WG_TILE;
+    if (family == WG_PIECES) {
         IGAN_REQUIRE((p->x_pieces == nullptr && p->dy_pieces == nullptr) || planes_mode() == 1, "conv2d_wgrad: the two-piece fp16 form writes its own images (one scale per channel): x_pieces / dy_pieces must be NULL");
         IGAN_REQUIRE(p->x_pieces == nullptr || p->x_pieces_bytes == wgrad_planes_x_floats(p) * 4, "conv2d_wgrad: x_pieces is not the image of this x (x_pieces_bytes != N*H*W*Cin*6)");
         IGAN_REQUIRE(p->dy_pieces == nullptr || p->dy_pieces_bytes == wgrad_planes_dy_floats(p) * 4, "conv2d_wgrad: dy_pieces is not the image of this dy (dy_pieces_bytes != N*OH*OW*Cout*6)");
@@ -3680,25 +3550,13 @@ extern "C" int igan_conv2d_wgrad(igan_stream_t stream_, const igan_conv2d_wgrad_
         if (planes_mode() == 2) hipLaunchKernelGGL((conv_wgrad_planes_kernel<2>), grid, dim3(512), 0, stream, a);
         else hipLaunchKernelGGL((conv_wgrad_planes_kernel<3>), grid, dim3(512), 0, stream, a);
         IGAN_LAUNCH_CHECK("conv2d_wgrad (piece form) launch");
-        if (splits > 1) {
-            const int total = (int)wsize;
-            const int rg = std::min(ceil_div(total, 256), 2048);
-            hipLaunchKernelGGL(plain_reduce_kernel, dim3(rg), dim3(256), 0, stream, (const float*)p->workspace, p->dw, total, splits, p->alpha);
-            IGAN_LAUNCH_CHECK("conv2d_wgrad reduce launch");
-        }
-        return IGAN_OK;
+    } else {                // WG_TILE: the (wm, wn) of choose_wgrad(), spelled as template arguments
+        if (t.BM == 128 && t.BN == 128 && c.wn == 4) launch_wgrad<128, 128, 2, 4>(stream, a, grid, c.vec, c.scm);
+        else if (t.BM == 128 && t.BN == 128) launch_wgrad<128, 128, 2, 2>(stream, a, grid, c.vec, c.scm);
+        else if (t.BM == 128 && t.BN == 32) launch_wgrad<128, 32, 4, 1>(stream, a, grid, c.vec, c.scm);
+        else launch_wgrad<32, 128, 1, 4>(stream, a, grid, c.vec, c.scm);
+        IGAN_LAUNCH_CHECK("conv2d_wgrad launch");
     }
-    const bool vec = a.vecA && a.vecB && (a.in_scale == nullptr || a.vecSA) && (a.out_scale == nullptr || a.vecSB);
-    const int scm = (a.in_scale && a.out_scale) ? 1 : ((a.in_scale || a.out_scale) ? 2 : 0);
-    // 8 waves pay on the short pixel axes (32x32 and below: +1.5 %), 4 waves on the 128x128 layers (+3-4 %): measured, tools/conv_bench.py
-    const bool long_axis = (long long)p->OH * p->OW >= 128LL * 128LL;
-    // (round 6) the scaled forms (scm != 0: the modulated layers below the piece form's row threshold) take the four-wave tile: at the 128 registers of eight waves they
-    // spill ten registers to scratch inside the loop (tools/asm_scan.py), at 256 they do not
-    if (t.BM == 128 && t.BN == 128 && eight_waves("IGAN_WGRAD_8WAVE") && !long_axis && scm == 0) launch_wgrad<128, 128, 2, 4>(stream, a, grid, vec, scm);
-    else if (t.BM == 128 && t.BN == 128) launch_wgrad<128, 128, 2, 2>(stream, a, grid, vec, scm);
-    else if (t.BM == 128 && t.BN == 32) launch_wgrad<128, 32, 4, 1>(stream, a, grid, vec, scm);
-    else launch_wgrad<32, 128, 1, 4>(stream, a, grid, vec, scm);
-    IGAN_LAUNCH_CHECK("conv2d_wgrad launch");
     if (splits > 1) {
         const int total = (int)wsize;
         const int rg = std::min(ceil_div(total, 256), 2048);

@@ -1,0 +1,68 @@
+// The ONE definition of the exact distance that nn1.hip (IMLE 1-NN) and knn_manifold.hip (pr50k3) share.
+// The radii the manifold search produces, the distances it compares with them and the 1-NN distances are the SAME function of
+// two rows (symmetric, d2(a, a) == 0, summation order fixed by dim and the 16-byte alignment of the rows alone) because both
+// files compile these definitions; the screening product and its error interval are shared for the same reason.
+#pragma once
+#include "igan_common.h"
+#include <cmath>
+
+namespace igan {
+
+// Relative half-width of the interval the fp32 cancellation form |q|^2 + |c|^2 - 2 q.c is trusted to: the dot product is an
+// fp32 FMA chain of `dim` terms (error ~ 0.3 * 2^-24 * sqrt(dim) * |q.c| statistically; measured 3.5e-7 * sum|a b| at dim 4096),
+// the norms are fp64 sums rounded to fp32.  2^-22 * sqrt(dim) (5.3e-5 at dim 49 152) leaves an order of magnitude of margin;
+// a wider interval only costs more exact evaluations, never a wrong answer.
+__device__ __forceinline__ double nn1_tol(int dim) { return fmax(2.384185791015625e-07 * sqrt((double)dim), 1e-6); }
+
+// Squared distance of two rows as a direct difference with fp64 accumulation (compute_dist, dci_code/src/util.c:62-69,
+// before its sqrt), by one whole wavefront; the result is in every lane.  Fixed summation order: deterministic.
+__device__ __forceinline__ double wave_sqdist(const float* __restrict__ a, const float* __restrict__ b, int dim, int lane) {
+    double s0 = 0.0, s1 = 0.0;
+    int i = lane * 4;
+    if ((dim & 3) == 0 && ((((uintptr_t)a | (uintptr_t)b) & 15) == 0)) {
+        for (; i + 256 < dim; i += 512) {      // two 16 B loads per operand in flight
+            const float4 x0 = *reinterpret_cast<const float4*>(a + i), y0 = *reinterpret_cast<const float4*>(b + i);
+            const float4 x1 = *reinterpret_cast<const float4*>(a + i + 256), y1 = *reinterpret_cast<const float4*>(b + i + 256);
+            double d;
+            d = (double)x0.x - (double)y0.x; s0 += d * d; d = (double)x0.y - (double)y0.y; s0 += d * d;
+            d = (double)x0.z - (double)y0.z; s0 += d * d; d = (double)x0.w - (double)y0.w; s0 += d * d;
+            d = (double)x1.x - (double)y1.x; s1 += d * d; d = (double)x1.y - (double)y1.y; s1 += d * d;
+            d = (double)x1.z - (double)y1.z; s1 += d * d; d = (double)x1.w - (double)y1.w; s1 += d * d;
+        }
+        for (; i < dim; i += 256) {
+            const float4 x0 = *reinterpret_cast<const float4*>(a + i), y0 = *reinterpret_cast<const float4*>(b + i);
+            double d;
+            d = (double)x0.x - (double)y0.x; s0 += d * d; d = (double)x0.y - (double)y0.y; s0 += d * d;
+            d = (double)x0.z - (double)y0.z; s0 += d * d; d = (double)x0.w - (double)y0.w; s0 += d * d;
+        }
+    } else {
+        for (int j = lane; j < dim; j += 64) {
+            const double d = (double)a[j] - (double)b[j];
+            s0 += d * d;
+        }
+    }
+    double s = s0 + s1;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+    return s;
+}
+
+// The [nq x dim] x [dim x nc] product q.c of a query batch and a candidate batch on the exact-fp32 MFMA: a 1x1 convolution with the
+// candidate matrix as a transposed filter -- both operands are read in their natural row-major [rows][dim] layout.
+inline int distance_products(igan_stream_t stream_, const float* query, const float* cand, float* dots, int nq, int nc, int dim) {
+    igan_conv2d_params p{};          // every optional field (epilogue, noise) zero
+    p.x = query; p.w = cand; p.y = dots;
+    p.in_scale = nullptr; p.out_scale = nullptr;
+    p.workspace = nullptr; p.workspace_floats = 0;
+    p.N = nq; p.H = 1; p.W = 1; p.Cin = dim;
+    p.OH = 1; p.OW = 1; p.Cout = nc;
+    p.KH = 1; p.KW = 1; p.stride = 1; p.up = 1; p.pad_y = 0; p.pad_x = 0;
+    p.w_transposed = 1;  // cand is [nc][dim] == forward-layout [1][1][Cout][Cin]
+    p.splits = 1;
+    p.sliced_tiles = 0;
+    p.alpha = 1.0f;
+    p.bias = nullptr; p.act = 0; p.act_alpha = 0.0f; p.act_gain = 1.0f;
+    return igan_conv2d(stream_, &p);
+}
+
+}  // namespace igan

@@ -11,46 +11,15 @@
 //   manifold_member_fold an any-within-radius reduction against per-candidate radii.
 // Both results are functions of exact distances only, hence independent of the order the batches arrive in.
 #include "igan_common.h"
+#include "exact_distance.h"
 
 #include <cmath>
 
 namespace {
 
-// nn1_tol and wave_sqdist are those of nn1.hip, statement for statement: the radii this file produces, the distances it
-// compares with them and the 1-NN distances are the SAME function of two rows (symmetric, d2(a, a) == 0, summation order
-// fixed by dim and the 16-byte alignment of the rows alone).
-__device__ __forceinline__ double nn1_tol(int dim) { return fmax(2.384185791015625e-07 * sqrt((double)dim), 1e-6); }
-
-__device__ __forceinline__ double wave_sqdist(const float* __restrict__ a, const float* __restrict__ b, int dim, int lane) {
-    double s0 = 0.0, s1 = 0.0;
-    int i = lane * 4;
-    if ((dim & 3) == 0 && ((((uintptr_t)a | (uintptr_t)b) & 15) == 0)) {
-        for (; i + 256 < dim; i += 512) {      // two 16 B loads per operand in flight
-            const float4 x0 = *reinterpret_cast<const float4*>(a + i), y0 = *reinterpret_cast<const float4*>(b + i);
-            const float4 x1 = *reinterpret_cast<const float4*>(a + i + 256), y1 = *reinterpret_cast<const float4*>(b + i + 256);
-            double d;
-            d = (double)x0.x - (double)y0.x; s0 += d * d; d = (double)x0.y - (double)y0.y; s0 += d * d;
-            d = (double)x0.z - (double)y0.z; s0 += d * d; d = (double)x0.w - (double)y0.w; s0 += d * d;
-            d = (double)x1.x - (double)y1.x; s1 += d * d; d = (double)x1.y - (double)y1.y; s1 += d * d;
-            d = (double)x1.z - (double)y1.z; s1 += d * d; d = (double)x1.w - (double)y1.w; s1 += d * d;
-        }
-        for (; i < dim; i += 256) {
-            const float4 x0 = *reinterpret_cast<const float4*>(a + i), y0 = *reinterpret_cast<const float4*>(b + i);
-            double d;
-            d = (double)x0.x - (double)y0.x; s0 += d * d; d = (double)x0.y - (double)y0.y; s0 += d * d;
-            d = (double)x0.z - (double)y0.z; s0 += d * d; d = (double)x0.w - (double)y0.w; s0 += d * d;
-        }
-    } else {
-        for (int j = lane; j < dim; j += 64) {
-            const double d = (double)a[j] - (double)b[j];
-            s0 += d * d;
-        }
-    }
-    double s = s0 + s1;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
-    return s;
-}
+// nn1_tol and wave_sqdist have ONE definition (exact_distance.h), which nn1.hip compiles too.
+using igan::nn1_tol;
+using igan::wave_sqdist;
 
 // Insert v into the ascending list l[0..KC) and drop the largest.  Static indices only: the list stays in registers.
 template <int KC>
@@ -202,24 +171,6 @@ __global__ __launch_bounds__(256) void manifold_member_fold_kernel(const float* 
     }
 }
 
-// The [nq x dim] x [dim x nc] product on the exact-fp32 MFMA, as igan_nn1_update takes it: a 1x1 convolution with the
-// candidate matrix as a transposed filter.
-int knn_products(igan_stream_t stream_, const float* query, const float* cand, float* dots, int nq, int nc, int dim) {
-    igan_conv2d_params p{};          // every optional field (epilogue, noise) zero
-    p.x = query; p.w = cand; p.y = dots;
-    p.in_scale = nullptr; p.out_scale = nullptr;
-    p.workspace = nullptr; p.workspace_floats = 0;
-    p.N = nq; p.H = 1; p.W = 1; p.Cin = dim;
-    p.OH = 1; p.OW = 1; p.Cout = nc;
-    p.KH = 1; p.KW = 1; p.stride = 1; p.up = 1; p.pad_y = 0; p.pad_x = 0;
-    p.w_transposed = 1;  // cand is [nc][dim] == forward-layout [1][1][Cout][Cin]
-    p.splits = 1;
-    p.sliced_tiles = 0;
-    p.alpha = 1.0f;
-    p.bias = nullptr; p.act = 0; p.act_alpha = 0.0f; p.act_gain = 1.0f;
-    return igan_conv2d(stream_, &p);
-}
-
 }  // namespace
 
 #define IGAN_KNN_REQUIRE_SIZES(name)                                                                                          \
@@ -235,7 +186,7 @@ extern "C" int igan_knn_radius_update(igan_stream_t stream_, const float* query,
     IGAN_REQUIRE(query && qnorm && cand && cnorm && kth_d2 && dots, "knn_radius_update: null buffer");
     IGAN_KNN_REQUIRE_SIZES("knn_radius_update");
     IGAN_REQUIRE(kcap >= 1 && kcap <= 16, "knn_radius_update: kcap must be in [1, 16]");
-    if (int rc = knn_products(stream_, query, cand, dots, nq, nc, dim)) return rc;
+    if (int rc = distance_products(stream_, query, cand, dots, nq, nc, dim)) return rc;
     const dim3 grid(ceil_div(nq, 4)), block(256);
     hipStream_t stream = (hipStream_t)stream_;
     if (kcap <= 4)
@@ -255,7 +206,7 @@ extern "C" int igan_manifold_member_update(igan_stream_t stream_, const float* q
     IGAN_REQUIRE(query && qnorm && cand && cnorm && cand_radius && member && dots, "manifold_member_update: null buffer");
     IGAN_KNN_REQUIRE_SIZES("manifold_member_update");
     IGAN_REQUIRE(nk >= 1 && nk <= 8, "manifold_member_update: nk must be in [1, 8]");
-    if (int rc = knn_products(stream_, query, cand, dots, nq, nc, dim)) return rc;
+    if (int rc = distance_products(stream_, query, cand, dots, nq, nc, dim)) return rc;
     hipLaunchKernelGGL(manifold_member_fold_kernel, dim3(ceil_div(nq, 4)), dim3(256), 0, (hipStream_t)stream_, dots, qnorm, cnorm,
                        query, cand, cand_radius, member, nq, nc, dim, nk);
     IGAN_LAUNCH_CHECK("manifold_member_fold launch");
