@@ -42,7 +42,7 @@ extern "C" {
  * 10: igan_knn_radius_update, igan_manifold_member_update; added under 10 without a bump, exports only: igan_ppl_endpoints, igan_ppl_crop_prep,
  * igan_linear_svc_workspace_bytes, igan_linear_svc_grad, igan_linear_svc_hv, igan_linear_svc_linesearch, igan_linear_svc_predict,
  * igan_images_to_uint8, igan_images_from_uint8, igan_dense_small2_grouped, igan_dense_small_wgrad2_grouped, igan_rows_group_sum,
- * igan_scale_add). */
+ * igan_scale_add, igan_kmeans_workspace_bytes, igan_kmeans_step). */
 #define IGAN_ABI_VERSION 10
 
 typedef void* igan_stream_t; /* hipStream_t */
@@ -526,6 +526,28 @@ int igan_manifold_member_update(igan_stream_t stream, const float* query, const 
                                 int* member /* [nq][nk], caller-initialised to 0 */,
                                 float* dots /* caller workspace, nq*nc floats */,
                                 int nq, int nc, int dim, int nk);
+
+/* ------------------------------------------------------------------------
+ * One exact k-means step for the PRD metric (reference: precision-recall-distributions/prd_score.py:125-127, the
+ * MiniBatchKMeans behind _cluster_into_bins): the nearest centre of every row and the per-centre sums of the rows.
+ *   (d2[i], label[i]) = lexicographic min over centres j of (|X_i - C_j|^2, j)
+ * with the squared distance of igan_nn1_update: the exact-fp32 MFMA product |x|^2 + |c|^2 - 2 x.c only screens (relative
+ * half-width 2^-22 * sqrt(dim) of |x|^2 + |c|^2), every centre the interval cannot rule out is measured as a direct
+ * difference in fp64 -- labels and d2 equal an fp64 brute force on the same fp32 rows, ties go to the lower index.  A row
+ * whose distances are all non-finite gets label -1 and d2 = +infinity and contributes to nothing below.
+ *   sums[j] = sum of X_i over label[i] == j, count[j] = the number of such rows, inertia[0] = sum of d2[i] over labelled rows
+ * all fp64, written (not accumulated); an empty cluster has count 0 and zero sums.  The order of every sum is a function of
+ * (n, k, dim) alone and there is no floating-point atomic: two calls give the same bits.
+ * xnorm / cnorm are the squared row norms (igan_row_sqnorm).  1 <= k <= 64 and 1 <= dim <= 4096 (IGAN_ERR_UNSUPPORTED
+ * beyond either); non-null buffers, n >= 1, n * dim * 4 below 2 GiB and n * k within int32 (IGAN_ERR_INVALID_ARGUMENT:
+ * longer row sets go in chunks, the caller adds the chunk results).  Arguments are validated before anything touches a
+ * device.  workspace: igan_kmeans_workspace_bytes(n, k, dim) bytes (0 for sizes outside the limits), 16-byte aligned,
+ * contents irrelevant.
+ */
+size_t igan_kmeans_workspace_bytes(int n, int k, int dim);
+int igan_kmeans_step(igan_stream_t stream, const float* X /* [n][dim] */, const float* xnorm, const float* C /* [k][dim] */,
+                     const float* cnorm, int* label /* [n] */, double* d2 /* [n] */, double* sums /* [k][dim] */,
+                     long long* count /* [k] */, double* inertia /* [1] */, void* workspace, int n, int k, int dim);
 
 /* ------------------------------------------------------------------------
  * Perceptual path length (reference: metrics/perceptual_path_length.py; ppl_zfull .. ppl2_wend).  Added without a

@@ -204,6 +204,8 @@ SIGNATURES = {
     'igan_nn1_update': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I]),
     'igan_knn_radius_update': (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I]),
     'igan_manifold_member_update': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I]),
+    'igan_kmeans_workspace_bytes': (_SZ, [_I, _I, _I]),
+    'igan_kmeans_step': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I]),
     'igan_ppl_endpoints': (_I, [_P, _P, _P, _P, _I, _I, ctypes.c_double, _I]),
     'igan_ppl_crop_prep': (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _LL, _LL, _LL, _LL]),
     'igan_linear_svc_workspace_bytes': (_SZ, [_I, _I, _I]),

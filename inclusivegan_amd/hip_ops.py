@@ -2224,6 +2224,59 @@ def manifold_member_update_raw(query, qnorm, cand, cnorm, cand_radius, member):
                                                _ptr(member), _ptr(dots), nq, nc, dim, nk))
 
 
+# ---- exact k-means step (csrc/kmeans.hip; the PRD metric) -------------------------------------------------------------------
+KMEANS_MAX_CLUSTERS = 64
+KMEANS_MAX_DIM = 4096
+
+
+def kmeans_step_raw(X, xnorm, C, cnorm, workspace=None):
+    """Nearest centre of every row of X [n, dim] among C [k, dim] (exact: an fp64 brute force on the same fp32 rows, ties to the
+    lower index) and the per-centre sums: -> label int32 [n] (-1: no finite distance), d2 fp64 [n], sums fp64 [k, dim],
+    count int64 [k], inertia fp64 [1], all on the device.  One launch sequence (igan_kmeans_step): n * dim * 4 below 2 GiB."""
+    lib = _abi.get_plugin()
+    _require_cuda_f32(X, xnorm, C, cnorm)
+    if X.dim() != 2 or C.dim() != 2 or C.shape[1] != X.shape[1] or xnorm.numel() != X.shape[0] or cnorm.numel() != C.shape[0]:
+        raise ValueError('kmeans_step: X must be [n, dim], C [k, dim], xnorm [n] and cnorm [k] (got %s, %s, %s, %s)'
+                         % (tuple(X.shape), tuple(C.shape), tuple(xnorm.shape), tuple(cnorm.shape)))
+    X, xnorm, C, cnorm = X.contiguous(), xnorm.contiguous(), C.contiguous(), cnorm.contiguous()
+    (n, dim), k = X.shape, C.shape[0]
+    dev = X.device
+    if workspace is None:
+        nbytes = int(lib.igan_kmeans_workspace_bytes(n, k, dim))
+        workspace = torch.empty(max(nbytes, 16) // 8 + 1, device=dev, dtype=torch.float64)    # an invalid size is reported by the call below
+    label = torch.empty(n, device=dev, dtype=torch.int32)
+    d2 = torch.empty(n, device=dev, dtype=torch.float64)
+    sums = torch.empty((k, dim), device=dev, dtype=torch.float64)
+    count = torch.empty(k, device=dev, dtype=torch.int64)
+    inertia = torch.empty(1, device=dev, dtype=torch.float64)
+    _abi.check(lib.igan_kmeans_step(_stream(), _ptr(X), _ptr(xnorm), _ptr(C), _ptr(cnorm), _ptr(label), _ptr(d2), _ptr(sums), _ptr(count),
+                                    _ptr(inertia), _ptr(workspace), n, k, dim))
+    return label, d2, sums, count, inertia
+
+
+def kmeans_step(X, xnorm, C, max_rows=None):
+    """kmeans_step_raw over any number of rows: X goes in chunks whose byte offsets stay within 32 bits (and the product block
+    within an int32 element count); sums, counts and inertia of the chunks are added in chunk order, in fp64."""
+    n, dim = X.shape
+    k = C.shape[0]
+    if not (1 <= k <= KMEANS_MAX_CLUSTERS and 1 <= dim <= KMEANS_MAX_DIM):
+        raise NotImplementedError('kmeans_step: 1 <= k <= %d and 1 <= dim <= %d (got k %d, dim %d)' % (KMEANS_MAX_CLUSTERS, KMEANS_MAX_DIM, k, dim))
+    fit = min(0x7FFFFFF0 // (4 * dim), (2 ** 31 - 1) // k)
+    step = fit if max_rows is None else max(1, min(int(max_rows), fit))
+    cnorm = row_sqnorm_raw(C)
+    if n <= step:
+        return kmeans_step_raw(X, xnorm, C, cnorm)
+    label = torch.empty(n, device=X.device, dtype=torch.int32)
+    d2 = torch.empty(n, device=X.device, dtype=torch.float64)
+    sums = count = inertia = None
+    for r0 in range(0, n, step):
+        l, d, s, c, i = kmeans_step_raw(X[r0:r0 + step], xnorm[r0:r0 + step], C, cnorm)
+        label[r0:r0 + step] = l
+        d2[r0:r0 + step] = d
+        sums, count, inertia = (s, c, i) if sums is None else (sums + s, count + c, inertia + i)
+    return label, d2, sums, count, inertia
+
+
 # ----------------------------------------------------------------------------
 # perceptual path length
 
