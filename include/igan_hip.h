@@ -42,7 +42,7 @@ extern "C" {
  * 10: igan_knn_radius_update, igan_manifold_member_update; added under 10 without a bump, exports only: igan_ppl_endpoints, igan_ppl_crop_prep,
  * igan_linear_svc_workspace_bytes, igan_linear_svc_grad, igan_linear_svc_hv, igan_linear_svc_linesearch, igan_linear_svc_predict,
  * igan_images_to_uint8, igan_images_from_uint8, igan_dense_small2_grouped, igan_dense_small_wgrad2_grouped, igan_rows_group_sum,
- * igan_scale_add, igan_kmeans_workspace_bytes, igan_kmeans_step). */
+ * igan_scale_add, igan_kmeans_workspace_bytes, igan_kmeans_step, igan_moments_workspace_bytes, igan_moments_update, igan_moments_finalize). */
 #define IGAN_ABI_VERSION 10
 
 typedef void* igan_stream_t; /* hipStream_t */
@@ -548,6 +548,33 @@ size_t igan_kmeans_workspace_bytes(int n, int k, int dim);
 int igan_kmeans_step(igan_stream_t stream, const float* X /* [n][dim] */, const float* xnorm, const float* C /* [k][dim] */,
                      const float* cnorm, int* label /* [n] */, double* d2 /* [n] */, double* sums /* [k][dim] */,
                      long long* count /* [k] */, double* inertia /* [1] */, void* workspace, int n, int k, int dim);
+
+/* ------------------------------------------------------------------------
+ * Streaming mean / covariance of feature rows for the FID metric (reference: metrics/frechet_inception_distance.py:43-44,64-65,
+ * np.mean and np.cov(rowvar=False) of the [num_images, 2048] activation block).  Added without a version bump: three more
+ * exports, no struct or signature changes.  Arguments are validated before anything touches a device.
+ *
+ * igan_moments_update ACCUMULATES one batch into caller-zeroed running statistics.  With d_ij = (double)X[i][j] - shift[j]
+ * (shift == NULL: 0):   sum[j] += sum_i d_ij,   gram[j][k] += sum_i d_ij * d_ik for j <= k; the lower triangle of gram is
+ * unspecified until finalize.  The conversion is exact, the subtraction rounds once, products and accumulation are fp64 on
+ * v_mfma_f64_16x16x4_f64 and sum is fp64 too.  Every 64 x 64 tile on or above the diagonal is owned by one workgroup, which
+ * walks the n rows in order and does the read-modify-write of its tile itself -- no split over n, no floating-point atomic:
+ * the bits are a function of (n, F) and the sequence of calls, and a repeated sequence gives identical bits.  Rows past n
+ * and columns past F contribute an exact 0 (the SHIFTED value is padded).  A NaN or infinity in X[i][j] reaches sum[j] and
+ * row / column j of gram as IEEE gives it and nothing else.  1 <= F <= 4096 (IGAN_ERR_UNSUPPORTED beyond); n >= 1, non-null
+ * X / sum / gram and n * F * 4 below 2 GiB (IGAN_ERR_INVALID_ARGUMENT; longer row sets go in several calls).  X needs 4-byte
+ * alignment only, shift / sum / gram 8-byte.  workspace: igan_moments_workspace_bytes(n, F) bytes -- 0 in this design, the
+ * pointer may be NULL.
+ *
+ * igan_moments_finalize WRITES, in fp64,   mean[j] = shift[j] + sum[j] / n_total   and, for j <= k,
+ *     cov[j][k] = cov[k][j] = (gram[j][k] - sum[j] * sum[k] / n_total) / (n_total - 1)             n_total >= 2
+ * With the shift near the mean the correction term is tiny and nothing cancels: on features 100 + 0.01 N(0, 1) a zero shift
+ * is wrong by 3.6e-7 of sqrt(cov_jj cov_kk), the mean of the first 8 rows as the shift by 1.4e-16.  cov must not alias gram. */
+size_t igan_moments_workspace_bytes(int n, int F);
+int igan_moments_update(igan_stream_t stream, const float* X /* [n][F] row-major */, const double* shift /* [F] or NULL */,
+                        double* sum /* [F] */, double* gram /* [F][F] */, void* workspace, size_t workspace_bytes, int n, int F);
+int igan_moments_finalize(igan_stream_t stream, const double* sum, const double* gram, const double* shift /* or NULL */,
+                          double* mean /* [F] */, double* cov /* [F][F] */, long long n_total, int F);
 
 /* ------------------------------------------------------------------------
  * Perceptual path length (reference: metrics/perceptual_path_length.py; ppl_zfull .. ppl2_wend).  Added without a

@@ -2277,6 +2277,110 @@ def kmeans_step(X, xnorm, C, max_rows=None):
     return label, d2, sums, count, inertia
 
 
+# ---- streaming mean / covariance (csrc/moments.hip; the FID metric) ---------------------------------------------------------
+MOMENTS_MAX_F = 4096
+MOMENTS_CHUNK_ROWS = 2048     # rows per igan_moments_update launch of FeatureMoments (tools/fid_bench.py records the choice)
+
+
+def _require_cuda_f64(name, *ts):
+    for t in ts:
+        if t is None:
+            continue
+        if not t.is_cuda:
+            raise RuntimeError('inclusivegan_amd kernels need tensors on a ROCm device (got %s); there is no CPU path' % t.device)
+        if t.dtype != torch.float64 or not t.is_contiguous():
+            raise TypeError('%s: the running statistics are contiguous float64 tensors (got %s)' % (name, t.dtype))
+
+
+def moments_update_raw(X, shift, sum_, gram):
+    """Fold the rows of X [n, F] fp32 (contiguous) into the running statistics (igan_moments_update): with d = X - shift in fp64
+    (shift None = 0), sum_ [F] += column sums of d and the upper triangle of gram [F, F] += d^T d, fp64 on the f64 matrix
+    instruction.  In place, no synchronisation; n * F * 4 below 2 GiB per call."""
+    lib = _abi.get_plugin()
+    _require_cuda_f32(X)
+    _require_cuda_f64('moments_update', shift, sum_, gram)
+    if X.dim() != 2 or not X.is_contiguous():
+        raise ValueError('moments_update: X must be a contiguous [n, F] matrix (got %s, strides %s)' % (tuple(X.shape), tuple(X.stride())))
+    n, F = (int(v) for v in X.shape)
+    if sum_.numel() != F or tuple(gram.shape) != (F, F) or (shift is not None and shift.numel() != F):
+        raise ValueError('moments_update: sum and shift must be [F] and gram [F, F] for X [n, F]')
+    nbytes = int(lib.igan_moments_workspace_bytes(n, F))
+    workspace = torch.empty(nbytes // 8 + 1, device=X.device, dtype=torch.float64) if nbytes else None
+    _abi.check(lib.igan_moments_update(_stream(), _ptr(X), _ptr(shift), _ptr(sum_), _ptr(gram), _ptr(workspace), nbytes, n, F))
+
+
+def moments_finalize_raw(sum_, gram, shift, n_total):
+    """(mean [F], cov [F, F]) fp64 on the device from the running statistics of n_total >= 2 rows (igan_moments_finalize):
+    mean = shift + sum / n, cov = (gram - sum sum^T / n) / (n - 1) from the upper triangle, symmetric bit for bit."""
+    lib = _abi.get_plugin()
+    _require_cuda_f64('moments_finalize', sum_, gram, shift)
+    F = int(sum_.numel())
+    if tuple(gram.shape) != (F, F) or (shift is not None and shift.numel() != F):
+        raise ValueError('moments_finalize: sum and shift must be [F] and gram [F, F]')
+    mean = torch.empty(F, device=sum_.device, dtype=torch.float64)
+    cov = torch.empty((F, F), device=sum_.device, dtype=torch.float64)
+    _abi.check(lib.igan_moments_finalize(_stream(), _ptr(sum_), _ptr(gram), _ptr(shift), _ptr(mean), _ptr(cov), int(n_total), F))
+    return mean, cov
+
+
+class FeatureMoments:
+    """Mean and covariance of a stream of feature batches, kept on the device (np.mean / np.cov(rowvar=False) of the rows seen).
+
+    update(features [b, F], any float dtype, on the device) stages the rows as fp32 in a [chunk_rows, F] buffer and launches one
+    igan_moments_update per full buffer, so the read-modify-write of the upper triangle (17 MB at F = 2048) is paid once per
+    chunk_rows rows and not once per minibatch.  The first batch fixes `shift`, its fp64 column mean.  Nothing in update()
+    synchronises; finalize() -> (mu [F], sigma [F, F]) as fp64 NumPy arrays is the one device -> host copy."""
+
+    def __init__(self, F, device, chunk_rows=MOMENTS_CHUNK_ROWS):
+        F, chunk_rows = int(F), int(chunk_rows)
+        if not 1 <= F <= MOMENTS_MAX_F:
+            raise NotImplementedError('FeatureMoments: 1 <= F <= %d (got %d)' % (MOMENTS_MAX_F, F))
+        if chunk_rows < 1:
+            raise ValueError('FeatureMoments: chunk_rows must be positive')
+        self.F, self.device = F, torch.device(device)
+        self.chunk_rows = min(chunk_rows, (2 ** 31 - 1) // (4 * F))
+        self.count = 0
+        self.shift = None
+        self._fill = 0
+        self._rows = torch.empty((self.chunk_rows, F), device=self.device, dtype=torch.float32)
+        self._sum = torch.zeros(F, device=self.device, dtype=torch.float64)
+        self._gram = torch.zeros((F, F), device=self.device, dtype=torch.float64)
+
+    def _flush(self):
+        if self._fill:
+            moments_update_raw(self._rows[:self._fill], self.shift, self._sum, self._gram)
+            self._fill = 0
+
+    def update(self, features):
+        if not torch.is_tensor(features) or not features.is_cuda:
+            raise RuntimeError('FeatureMoments.update: features must be a tensor on a ROCm device; there is no CPU path')
+        if features.dim() != 2 or features.shape[1] != self.F or not features.is_floating_point():
+            raise ValueError('FeatureMoments.update: features must be a float [b, %d] tensor (got %s %s)' % (self.F, features.dtype, tuple(features.shape)))
+        features = features.detach()
+        b = int(features.shape[0])
+        if b == 0:
+            return
+        if self.shift is None:      # a true division by a device scalar: the mean of a constant column is that constant
+            self.shift = features.to(torch.float64).sum(dim=0) / torch.full((), float(b), device=self.device, dtype=torch.float64)
+        done = 0
+        while done < b:
+            take = min(b - done, self.chunk_rows - self._fill)
+            self._rows[self._fill:self._fill + take].copy_(features[done:done + take])      # converts to fp32 on the way
+            self._fill += take
+            done += take
+            if self._fill == self.chunk_rows:
+                self._flush()
+        self.count += b
+
+    def finalize(self):
+        if self.count < 2:
+            raise ValueError('FeatureMoments.finalize: a covariance needs at least 2 rows (got %d)' % self.count)
+        self._flush()
+        mean, cov = moments_finalize_raw(self._sum, self._gram, self.shift, self.count)
+        both = torch.cat([mean, cov.reshape(-1)]).cpu().numpy()
+        return both[:self.F].copy(), both[self.F:].reshape(self.F, self.F).copy()
+
+
 # ----------------------------------------------------------------------------
 # perceptual path length
 

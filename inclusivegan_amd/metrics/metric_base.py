@@ -1,12 +1,13 @@
 """Common definitions for the quality metrics (reference: metrics/metric_base.py:22-165).
 
 Kept: `MetricBase` (name, `run(network_pkl | Gs, ...)`, `_report_result`, `get_result_str` in the reference's line format,
-`_iterate_reals` / `_iterate_fakes`), `MetricGroup`, `DummyMetric`.  What changes: the reference opens three more pickles
+`_iterate_reals` / `_iterate_fakes`, `_get_cache_file_for_reals`), `MetricGroup`, `DummyMetric`.  What changes: the reference opens three more pickles
 (Inception-v3 features, the Stacked-MNIST classifier: .MISSING_LARGE_BLOBS) that are not available here, so every metric
 takes the network that turns uint8 images into features / logits as an INJECTED callable (`feature_fn`, `classify_fn`);
 the statistics on top of them (the FID formula, mode count, KL to uniform) are the reference's, value for value
 (tests/test_metrics.py pins them to the reference's own statements).  Fakes come from Gs on this engine's HIP path.
 """
+import hashlib
 import os
 import time
 
@@ -91,6 +92,28 @@ class MetricBase:
         from ..dnnlib.tflib.autosummary import autosummary
         for r in self._results:
             autosummary('Metrics/%s%s' % (self.name, r.suffix), r.value)
+
+    # ---- cache of real statistics (metric_base.py:110-117) -------------------------------------------------------------------
+    def _get_cache_file_for_reals(self, extension='pkl', feature_fn=None, **kwargs):
+        """`.stylegan2-cache/<md5>-<metric name>-<dataset>.<extension>` with the reference's hash: md5 of repr(sorted(items)) over
+        metric_name, mirror_augment, the dataset args and the kwargs.  The injected network is part of what the file holds, so
+        `feature_fn` enters the hash as `__module__.__qualname__`.  None -- nothing is read or written -- when the dataset
+        args name no `tfrecord_dir`, or when the callable has no importable name (a lambda, a local function, an object)."""
+        dataset_args = dict(self._dataset_args or {})
+        dataset_name = dataset_args.get('tfrecord_dir', None)
+        if not dataset_name:
+            return None
+        all_args = dict(metric_name=self.name, mirror_augment=self._mirror_augment)
+        all_args.update(dataset_args)
+        all_args.update(kwargs)
+        if feature_fn is not None:
+            qualname, module = getattr(feature_fn, '__qualname__', None), getattr(feature_fn, '__module__', None)
+            if not qualname or not module or '<' in qualname:
+                return None
+            all_args['feature_fn'] = module + '.' + qualname
+        md5 = hashlib.md5(repr(sorted(all_args.items())).encode('utf-8'))
+        dataset_name = os.path.splitext(os.path.basename(dataset_name))[0]
+        return os.path.join('.stylegan2-cache', '%s-%s-%s.%s' % (md5.hexdigest(), self.name, dataset_name, extension))
 
     # ---- data ----------------------------------------------------------------------------------------------------------
     def _get_dataset_obj(self):
