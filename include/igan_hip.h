@@ -42,7 +42,8 @@ extern "C" {
  * 10: igan_knn_radius_update, igan_manifold_member_update; added under 10 without a bump, exports only: igan_ppl_endpoints, igan_ppl_crop_prep,
  * igan_linear_svc_workspace_bytes, igan_linear_svc_grad, igan_linear_svc_hv, igan_linear_svc_linesearch, igan_linear_svc_predict,
  * igan_images_to_uint8, igan_images_from_uint8, igan_dense_small2_grouped, igan_dense_small_wgrad2_grouped, igan_rows_group_sum,
- * igan_scale_add, igan_kmeans_workspace_bytes, igan_kmeans_step, igan_moments_workspace_bytes, igan_moments_update, igan_moments_finalize). */
+ * igan_scale_add, igan_kmeans_workspace_bytes, igan_kmeans_step, igan_moments_workspace_bytes, igan_moments_update, igan_moments_finalize,
+ * igan_moments_merge). */
 #define IGAN_ABI_VERSION 10
 
 typedef void* igan_stream_t; /* hipStream_t */
@@ -569,12 +570,27 @@ int igan_kmeans_step(igan_stream_t stream, const float* X /* [n][dim] */, const 
  * igan_moments_finalize WRITES, in fp64,   mean[j] = shift[j] + sum[j] / n_total   and, for j <= k,
  *     cov[j][k] = cov[k][j] = (gram[j][k] - sum[j] * sum[k] / n_total) / (n_total - 1)             n_total >= 2
  * With the shift near the mean the correction term is tiny and nothing cancels: on features 100 + 0.01 N(0, 1) a zero shift
- * is wrong by 3.6e-7 of sqrt(cov_jj cov_kk), the mean of the first 8 rows as the shift by 1.4e-16.  cov must not alias gram. */
+ * is wrong by 3.6e-7 of sqrt(cov_jj cov_kk), the mean of the first 8 rows as the shift by 1.4e-16.  cov must not alias gram.
+ *
+ * igan_moments_merge (one more export under version 10) FOLDS state B -- n_b rows about shift_b -- into state A, re-expressed
+ * about A's shift, without reading a feature row again: with dl_j = shift_b[j] - shift_a[j] (a NULL shift is 0)
+ *     sum_a[j]     += sum_b[j] + n_b dl_j
+ *     gram_a[j][k] += gram_b[j][k] + dl_j sum_b[k] + sum_b[j] dl_k + n_b dl_j dl_k                  for j <= k only
+ * This is how the statistics of several ranks become one (FeatureMoments.all_merge: every rank folds the ranks' states in
+ * rank order and ends with the same bits).  All fp64; one thread owns each output element of the 64 x 64 tiles on or above
+ * the diagonal (the diagonal tile's workgroup owns sum), no atomic and no reduction: the bits are a function of the inputs
+ * alone.  The lower triangle of gram_a stays unspecified until finalize; the strict lower triangle of gram_b is never read;
+ * B is not written, shift_a is not changed and the caller adds the counts.  A non-finite sum_b[j], gram_b[j][.] or
+ * shift_*[j] reaches sum_a[j] and row / column j of gram_a and nothing else: every operand of element (j, k) carries index
+ * j or k.  F > 4096: IGAN_ERR_UNSUPPORTED; F < 1, n_b < 1, a null sum / gram, sum_a == sum_b, gram_a == gram_b or a pointer
+ * that is not 8-byte aligned: IGAN_ERR_INVALID_ARGUMENT. */
 size_t igan_moments_workspace_bytes(int n, int F);
 int igan_moments_update(igan_stream_t stream, const float* X /* [n][F] row-major */, const double* shift /* [F] or NULL */,
                         double* sum /* [F] */, double* gram /* [F][F] */, void* workspace, size_t workspace_bytes, int n, int F);
 int igan_moments_finalize(igan_stream_t stream, const double* sum, const double* gram, const double* shift /* or NULL */,
                           double* mean /* [F] */, double* cov /* [F][F] */, long long n_total, int F);
+int igan_moments_merge(igan_stream_t stream, double* sum_a, double* gram_a, const double* shift_a /* [F] or NULL = 0 */,
+                       const double* sum_b, const double* gram_b, const double* shift_b /* [F] or NULL = 0 */, long long n_b, int F);
 
 /* ------------------------------------------------------------------------
  * Perceptual path length (reference: metrics/perceptual_path_length.py; ppl_zfull .. ppl2_wend).  Added without a

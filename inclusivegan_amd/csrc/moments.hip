@@ -127,6 +127,38 @@ __global__ __launch_bounds__(256) void moments_finalize_kernel(const double* __r
     if (r == 0) mean[c] = (shift ? shift[c] : 0.0) + sum[c] / n_total;
 }
 
+// State B (n_b rows about shift_b) folded into state A, re-expressed about A's shift: with e_ij = x_ij - shift_b[j] and
+// dl_j = shift_b[j] - shift_a[j], x_ij - shift_a[j] = e_ij + dl_j, hence
+//   sum_i (e_ij + dl_j)               = sumB_j + n_b dl_j
+//   sum_i (e_ij + dl_j) (e_ik + dl_k) = gramB_jk + dl_j sumB_k + sumB_j dl_k + n_b dl_j dl_k.
+// Same tiling as moments_update_kernel; thread t owns column (t & 63) of rows (t >> 6) + 4 i of its tile and does the one
+// read-modify-write of each element: no atomic, no reduction.  Every operand of element (j, k) carries index j or k, so a
+// non-finite value at index m reaches row / column m only (there is no product with an operand of a third index).  Only
+// j <= k of gram_b is read.
+__global__ __launch_bounds__(MOM_NT) void moments_merge_kernel(double* __restrict__ sum_a, double* __restrict__ gram_a,
+                                                               const double* __restrict__ shift_a, const double* __restrict__ sum_b,
+                                                               const double* __restrict__ gram_b, const double* __restrict__ shift_b,
+                                                               double n_b, int F) {
+    const int tk = blockIdx.x, tj = blockIdx.y;
+    if (tj > tk) return;                                   // tiles on or above the diagonal only (uniform per workgroup)
+    const int t = threadIdx.x;
+    const int c = t & 63, rsub = t >> 6;
+    const int k = tk * MOM_TILE + c;
+    if (k >= F) return;                                    // no barrier below: a thread past the last column has nothing to do
+    const double dk = (shift_b ? shift_b[k] : 0.0) - (shift_a ? shift_a[k] : 0.0);
+    const double sk = sum_b[k];
+    const double right = sk + n_b * dk;                    // dl_j * right = dl_j sumB_k + n_b dl_j dl_k
+#pragma unroll 4
+    for (int i = 0; i < MOM_TILE / 4; i++) {
+        const int j = tj * MOM_TILE + 4 * i + rsub;
+        if (j > k) continue;                               // j <= k < F
+        const double dj = (shift_b ? shift_b[j] : 0.0) - (shift_a ? shift_a[j] : 0.0);
+        const size_t at = (size_t)j * F + k;
+        gram_a[at] += gram_b[at] + (dj * right + sum_b[j] * dk);
+    }
+    if (tj == tk && rsub == 0) sum_a[k] += right;
+}
+
 }  // namespace
 
 extern "C" size_t igan_moments_workspace_bytes(int n, int F) {
@@ -160,5 +192,22 @@ extern "C" int igan_moments_finalize(igan_stream_t stream_, const double* sum, c
     hipLaunchKernelGGL(moments_finalize_kernel, dim3(ceil_div(F, 64), ceil_div(F, 4)), dim3(256), 0, (hipStream_t)stream_, sum, gram, shift,
                        mean, cov, (double)n_total, F);
     IGAN_LAUNCH_CHECK("moments_finalize launch");
+    return IGAN_OK;
+}
+
+extern "C" int igan_moments_merge(igan_stream_t stream_, double* sum_a, double* gram_a, const double* shift_a, const double* sum_b,
+                                  const double* gram_b, const double* shift_b, long long n_b, int F) {
+    using namespace igan;
+    if (F > MOM_MAX_F) return fail(IGAN_ERR_UNSUPPORTED, "moments_merge: 1 <= F <= 4096");
+    IGAN_REQUIRE(F >= 1, "moments_merge: F must be positive (1 <= F <= 4096)");
+    IGAN_REQUIRE(n_b >= 1, "moments_merge: n_b must be positive (an empty state is skipped by the caller)");
+    IGAN_REQUIRE(sum_a && gram_a && sum_b && gram_b, "moments_merge: null buffer");
+    IGAN_REQUIRE(sum_a != sum_b && gram_a != gram_b, "moments_merge: state B must not alias state A");
+    IGAN_REQUIRE(((((uintptr_t)sum_a) | ((uintptr_t)gram_a) | ((uintptr_t)shift_a) | ((uintptr_t)sum_b) | ((uintptr_t)gram_b) | ((uintptr_t)shift_b)) & 7) == 0,
+                 "moments_merge: shift / sum / gram must be 8-byte aligned");
+    const int tiles = ceil_div(F, MOM_TILE);
+    hipLaunchKernelGGL(moments_merge_kernel, dim3(tiles, tiles), dim3(MOM_NT), 0, (hipStream_t)stream_, sum_a, gram_a, shift_a, sum_b, gram_b,
+                       shift_b, (double)n_b, F);
+    IGAN_LAUNCH_CHECK("moments_merge launch");
     return IGAN_OK;
 }

@@ -115,6 +115,30 @@ class _DefaultRandom:
         return [t.view(sh) for t, sh in zip(torch.split(flat, sizes), shapes)]
 
 
+class SeededRandom(_DefaultRandom):
+    """The default draws from a PRIVATE device generator: a stream that depends on `seed` alone and leaves the process's
+    global device generator where it was (the multi-rank metrics: one seed per rank, training draws untouched)."""
+
+    def __init__(self, device, seed):
+        self.generator = torch.Generator(device=device)
+        self.generator.manual_seed(int(seed))
+
+    def normal(self, shape, device):
+        return torch.randn(tuple(int(s) for s in shape), device=device, dtype=torch.float32, generator=self.generator)
+
+    def uniform(self, shape, device, minval=0.0, maxval=1.0):
+        return torch.rand(tuple(int(s) for s in shape), device=device, dtype=torch.float32, generator=self.generator) * (maxval - minval) + minval
+
+    def randint(self, low, high, device):
+        return torch.randint(int(low), int(high), (), device=device, generator=self.generator)
+
+    def normal_many(self, shapes, device):
+        shapes = [tuple(int(s) for s in sh) for sh in shapes]
+        sizes = [int(np.prod(sh)) for sh in shapes]
+        flat = torch.randn((sum(sizes),), device=device, dtype=torch.float32, generator=self.generator)
+        return [t.view(sh) for t, sh in zip(torch.split(flat, sizes), shapes)]
+
+
 class RandomTape:
     """Replays tensors in call order: entries are (kind, array-like). Raises when exhausted or on a
     kind/shape mismatch, so a test that injects the wrong number of random draws fails loudly."""

@@ -2323,13 +2323,30 @@ def moments_finalize_raw(sum_, gram, shift, n_total):
     return mean, cov
 
 
+def moments_merge_raw(sum_a, gram_a, shift_a, sum_b, gram_b, shift_b, n_b):
+    """Fold state B (n_b rows about shift_b) into state A, re-expressed about shift_a (igan_moments_merge): with
+    dl = shift_b - shift_a (None = 0), sum_a += sum_b + n_b dl and, on the upper triangle, gram_a += gram_b + dl sum_b^T +
+    sum_b dl^T + n_b dl dl^T; fp64, one owner per element.  In place, no synchronisation; B is only read and the caller adds
+    the counts."""
+    lib = _abi.get_plugin()
+    _require_cuda_f64('moments_merge', sum_a, gram_a, shift_a, sum_b, gram_b, shift_b)
+    F = int(sum_a.numel())
+    if (tuple(gram_a.shape) != (F, F) or tuple(gram_b.shape) != (F, F) or sum_b.numel() != F
+            or any(s is not None and s.numel() != F for s in (shift_a, shift_b))):
+        raise ValueError('moments_merge: sum and shift must be [F] and gram [F, F] on both sides')
+    if any(t is not None and t.device != sum_a.device for t in (gram_a, shift_a, sum_b, gram_b, shift_b)):
+        raise ValueError('moments_merge: both states must live on one device')
+    _abi.check(lib.igan_moments_merge(_stream(), _ptr(sum_a), _ptr(gram_a), _ptr(shift_a), _ptr(sum_b), _ptr(gram_b), _ptr(shift_b), int(n_b), F))
+
+
 class FeatureMoments:
     """Mean and covariance of a stream of feature batches, kept on the device (np.mean / np.cov(rowvar=False) of the rows seen).
 
     update(features [b, F], any float dtype, on the device) stages the rows as fp32 in a [chunk_rows, F] buffer and launches one
     igan_moments_update per full buffer, so the read-modify-write of the upper triangle (17 MB at F = 2048) is paid once per
     chunk_rows rows and not once per minibatch.  The first batch fixes `shift`, its fp64 column mean.  Nothing in update()
-    synchronises; finalize() -> (mu [F], sigma [F, F]) as fp64 NumPy arrays is the one device -> host copy."""
+    synchronises; finalize() -> (mu [F], sigma [F, F]) as fp64 NumPy arrays is the one device -> host copy.  merge(other) folds
+    another state in (igan_moments_merge: the two shifts differ), all_merge(group) gives every rank the union of all ranks' rows."""
 
     def __init__(self, F, device, chunk_rows=MOMENTS_CHUNK_ROWS):
         F, chunk_rows = int(F), int(chunk_rows)
@@ -2379,6 +2396,64 @@ class FeatureMoments:
         mean, cov = moments_finalize_raw(self._sum, self._gram, self.shift, self.count)
         both = torch.cat([mean, cov.reshape(-1)]).cpu().numpy()
         return both[:self.F].copy(), both[self.F:].reshape(self.F, self.F).copy()
+
+    def merge(self, other):
+        """Fold the rows `other` has seen into this state, as if update() had been given them too (moments add once both are
+        about one shift: igan_moments_merge).  `other` stays usable and unchanged; nothing here synchronises."""
+        if not isinstance(other, FeatureMoments) or other is self:
+            raise ValueError('FeatureMoments.merge: the other side must be another FeatureMoments')
+        if other.F != self.F or other.device != self.device:
+            raise ValueError('FeatureMoments.merge: both sides must have one F and one device (got %d on %s and %d on %s)'
+                             % (self.F, self.device, other.F, other.device))
+        self._flush()
+        other._flush()
+        if other.count == 0:
+            return self
+        if self.count == 0:
+            self.shift = other.shift.clone()
+            self._sum.copy_(other._sum)
+            self._gram.copy_(other._gram)
+        else:
+            moments_merge_raw(self._sum, self._gram, self.shift, other._sum, other._gram, other.shift, other.count)
+        self.count += other.count
+        return self
+
+    def all_merge(self, group=None):
+        """Every rank of `group` (None: the default group) ends with the union of all ranks' rows, bit for bit the same state.
+        Rank by rank, the owner broadcasts (count, shift, sum) as one fp64 vector and its gram matrix; every rank folds them,
+        in rank order, into a fresh state, so the shift of the result is that of the first rank that saw a row and ranks that
+        saw none are skipped by everyone.  Next to the result, one F x F matrix of scratch whatever the world size (the owner
+        sends its own matrix, the others receive into the scratch).  A collective: it synchronises
+        (the counts are read on the host)."""
+        dist = torch.distributed
+        world, rank = dist.get_world_size(group), dist.get_rank(group)
+        self._flush()
+        F = self.F
+        head = torch.empty(1 + 2 * F, device=self.device, dtype=torch.float64)
+        scratch = torch.empty((F, F), device=self.device, dtype=torch.float64)
+        total = FeatureMoments(F, self.device, chunk_rows=1)      # only its statistics are kept; this object keeps its own row buffer
+        for r in range(world):
+            src = r if group is None else dist.get_global_rank(group, r)
+            if r == rank:
+                head[0] = float(self.count)
+                head[1:1 + F] = self.shift if self.shift is not None else 0.0
+                head[1 + F:] = self._sum
+            dist.broadcast(head, src, group=group)
+            count = int(head[0].item())
+            if count == 0:
+                continue
+            gram = self._gram if r == rank else scratch
+            dist.broadcast(gram, src, group=group)
+            shift_r, sum_r = head[1:1 + F].clone(), head[1 + F:].clone()
+            if total.count == 0:        # as merge() does: the first state is adopted, shift and all
+                total.shift = shift_r
+                total._sum.copy_(sum_r)
+                total._gram.copy_(gram)
+            else:
+                moments_merge_raw(total._sum, total._gram, total.shift, sum_r, gram, shift_r, count)
+            total.count += count
+        self.count, self.shift, self._sum, self._gram, self._fill = total.count, total.shift, total._sum, total._gram, 0
+        return self
 
 
 # ----------------------------------------------------------------------------

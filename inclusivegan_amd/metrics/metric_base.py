@@ -36,9 +36,12 @@ class MetricBase:
     """Harness of one metric (metric_base.py:22-130): `run()` evaluates it on a snapshot or a live Gs, `_evaluate()` (subclass)
     calls `_report_result()` once per number, `get_result_str()` renders the reference's line."""
 
+    multi_rank = False      # True: under a process group every rank evaluates a share (MetricGroup.run); False: rank 0 alone
+
     def __init__(self, name):
         self.name = name
         self._dataset_obj = None
+        self._process_group = None
         self._configure()
 
     # ---- per-run state -------------------------------------------------------------------------------------------------
@@ -56,16 +59,28 @@ class MetricBase:
 
     # ---- evaluation ----------------------------------------------------------------------------------------------------
     def run(self, network_pkl, run_dir=None, data_dir=None, dataset_args=None, mirror_augment=None, num_gpus=1, tf_config=None,
-            log_results=True, Gs_kwargs=dict(is_validation=True), device=None):
-        """`network_pkl`: a snapshot file (the last object of the pickled tuple is Gs, metric_base.py:66) or a live Gs Network."""
+            log_results=True, Gs_kwargs=dict(is_validation=True), device=None, process_group=None):
+        """`network_pkl`: a snapshot file (the last object of the pickled tuple is Gs, metric_base.py:66) or a live Gs Network.
+        `process_group`: None -- this process evaluates the whole metric, whether torch.distributed is initialised or not.  A
+        group -- every rank of it makes this call and evaluates its share (`multi_rank` metrics only); rank 0 alone reports,
+        prints and writes `metric-<name>.txt`, the other ranks end with no results."""
         from ..training import misc
+        if process_group is not None and not self.multi_rank:
+            raise ValueError('%s evaluates on one rank: call it without process_group (MetricGroup.run does so on rank 0)' % type(self).__name__)
         from_file = isinstance(network_pkl, str)
         self._configure(network_pkl if from_file else 'live-network', data_dir, dataset_args, mirror_augment)
+        self._process_group = process_group
         started = time.time()
         Gs = misc.as_networks(misc.load_pkl(network_pkl), device=device)[-1] if from_file else network_pkl
-        with torch.no_grad():
-            self._evaluate(Gs, Gs_kwargs=Gs_kwargs, num_gpus=num_gpus)
+        try:
+            with torch.no_grad():
+                self._evaluate(Gs, Gs_kwargs=Gs_kwargs, num_gpus=num_gpus)
+        finally:
+            self._process_group = None
         self._eval_time = time.time() - started
+        if process_group is not None and torch.distributed.get_rank(process_group) != 0:
+            self._results = []
+            return
         if not log_results:
             return
         line = self.get_result_str().strip()
@@ -142,11 +157,13 @@ class MetricBase:
         assert labels.shape == (minibatch_size, want), (labels.shape, want)
         return torch.from_numpy(labels).to(Gs.device)
 
-    def _generate(self, Gs, minibatch_size, Gs_kwargs, as_uint8=True):
+    def _generate(self, Gs, minibatch_size, Gs_kwargs, as_uint8=True, labels=None):
         """One minibatch of fakes from Gs: latents ~ N(0, I) on the device, label rows drawn from the data set (metric_base.py:139-146 /
-        the per-GPU graphs of the metric files), optionally converted like tflib.convert_images_to_uint8."""
+        the per-GPU graphs of the metric files; `labels`: rows the caller drew, e.g. a rank's rows of a global minibatch),
+        optionally converted like tflib.convert_images_to_uint8."""
         latents = tfutil.random_normal([minibatch_size] + Gs.input_shapes[0][1:], Gs.device)
-        labels = self._get_random_labels(minibatch_size, Gs)
+        if labels is None:
+            labels = self._get_random_labels(minibatch_size, Gs)
         images = Gs.get_output_for(latents, labels, **Gs_kwargs)
         return convert_images_to_uint8(images) if as_uint8 else images
 
@@ -165,9 +182,20 @@ class MetricGroup:
     def __init__(self, metric_kwarg_list):
         self.metrics = [dnnlib.util.call_func_by_name(**_retarget(kw)) for kw in metric_kwarg_list]
 
-    def run(self, *args, **kwargs):
+    def run(self, *args, process_group=None, **kwargs):
+        """`process_group` None: this process runs every metric.  A group: every rank makes this call; `multi_rank` metrics run
+        on all ranks, the others on rank 0 alone without the group, and one barrier at the end lets the ranks leave together."""
+        if process_group is None:
+            for m in self.metrics:
+                m.run(*args, **kwargs)
+            return
+        rank = torch.distributed.get_rank(process_group)
         for m in self.metrics:
-            m.run(*args, **kwargs)
+            if m.multi_rank:
+                m.run(*args, process_group=process_group, **kwargs)
+            elif rank == 0:
+                m.run(*args, **kwargs)
+        torch.distributed.barrier(group=process_group)
 
     def get_result_str(self):
         return ' '.join(m.get_result_str() for m in self.metrics)

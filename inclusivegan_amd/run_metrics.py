@@ -30,14 +30,18 @@ def _with_injected(metric_args, inject):
     return args
 
 
-def run(network_pkl, metrics, dataset, data_dir, mirror_augment, num_gpus=1, run_dir=None, inject=None):
-    print('Evaluating metrics "%s" for "%s"...' % (','.join(metrics), network_pkl))
+def run(network_pkl, metrics, dataset, data_dir, mirror_augment, num_gpus=1, run_dir=None, inject=None, process_group=None):
+    """`process_group` None: this process evaluates everything (`num_gpus` scales the minibatch on its one device).  A group: every
+    rank makes this call; metrics that spread over ranks (fid*) do, the others run on rank 0; pass `run_dir` on rank 0 only."""
+    if process_group is None or run_dir is not None:
+        print('Evaluating metrics "%s" for "%s"...' % (','.join(metrics), network_pkl))
     network_pkl = pretrained_networks.get_path_or_url(network_pkl)
     dataset_args = dnnlib.EasyDict(tfrecord_dir=dataset, shuffle_mb=0, max_label_size='full')
     metric_group = metric_base.MetricGroup([_with_injected(metric_defaults[metric], inject) for metric in metrics])
     if run_dir is not None:
         os.makedirs(run_dir, exist_ok=True)
-    metric_group.run(network_pkl, run_dir=run_dir, data_dir=data_dir, dataset_args=dataset_args, mirror_augment=mirror_augment, num_gpus=num_gpus)
+    metric_group.run(network_pkl, run_dir=run_dir, data_dir=data_dir, dataset_args=dataset_args, mirror_augment=mirror_augment, num_gpus=num_gpus,
+                     process_group=process_group)
     return metric_group
 
 #----------------------------------------------------------------------------
@@ -75,10 +79,30 @@ def main(argv=None):
         print('Error: dataset root directory does not exist.')
         sys.exit(1)
 
+    # one process per GPU, as run_training.main has it: the launcher sets RANK / WORLD_SIZE / LOCAL_RANK
+    rank, world, local_rank = (int(os.environ.get(k, d)) for k, d in (('RANK', '0'), ('WORLD_SIZE', '1'), ('LOCAL_RANK', '0')))
+    if args.num_gpus != world:
+        print('Error: --num-gpus %d needs %d processes, one per GPU, and this job has %d.  Launch it as\n'
+              '    python -m torch.distributed.run --nproc-per-node %d -m inclusivegan_amd.run_metrics --num-gpus %d ...'
+              % (args.num_gpus, args.num_gpus, world, args.num_gpus, args.num_gpus))
+        sys.exit(1)
+    import torch
+    torch.cuda.set_device(local_rank)
+    process_group = None
+    if world > 1:
+        os.environ.setdefault('MASTER_ADDR', '127.0.0.1')
+        import datetime
+        # generous timeout: the metrics that do not spread over ranks run on rank 0 while the others wait at the closing barrier
+        torch.distributed.init_process_group('nccl', timeout=datetime.timedelta(hours=4))
+        process_group = torch.distributed.group.WORLD
+
     kwargs = vars(args)
     inject = {key: dnnlib.util.get_obj_by_name(name) for key, name in (kwargs.pop('inject') or [])}
-    run_dir = next_run_dir(kwargs.pop('result_dir'), 'run-metrics')
-    run(run_dir=run_dir, inject=inject, **kwargs)
+    result_dir = kwargs.pop('result_dir')
+    run_dir = next_run_dir(result_dir, 'run-metrics') if rank == 0 else None      # rank 0 alone creates it and reports into it
+    run(run_dir=run_dir, inject=inject, process_group=process_group, **kwargs)
+    if world > 1:
+        torch.distributed.destroy_process_group()
 
 #----------------------------------------------------------------------------
 

@@ -539,6 +539,14 @@ def training_loop(
     sched = training_schedule(cur_nimg=0, training_set=training_set, **sched_args)
     from ..metrics import metric_base
     metrics = metric_base.MetricGroup(metric_arg_list)       # :198
+    # World > 1: the snapshot metrics are evaluated by all ranks (MetricGroup.run under the world group) unless IGAN_METRICS_RANKS=0
+    # asks for rank 0 alone.  Only rank 0 is given the run directory, so it tells the others where the snapshots go.
+    metrics_all_ranks, snapshot_dir = False, None
+    if world > 1 and metrics.metrics and os.environ.get('IGAN_METRICS_RANKS', '1') != '0':
+        box = [run_dir if rank == 0 else None]
+        torch.distributed.broadcast_object_list(box, src=0)
+        snapshot_dir = box[0]
+        metrics_all_ranks = snapshot_dir is not None
 
     # Setup optimizers (:242-255).
     cur_lrate = [sched.G_lrate]
@@ -907,13 +915,24 @@ def training_loop(
                         fakes_nn = Gs.run(t_latents, t_labels, is_validation=True, minibatch_size=sched.minibatch_gpu)
                         misc.save_image_grid(fakes_nn, snap('rec-fakes-%06d.png' % (cur_nimg // 1000)), drange=drange_net, grid_size=rec_grid)
                         final_grids = (grid_fakes, fakes_nn, rec_grid)
-                if network_snapshot_ticks is not None and (cur_tick % max(network_snapshot_ticks, 1) == 0 or done):
+                if network_snapshot_ticks is not None and (cur_tick % max(network_snapshot_ticks, 1) == 0 or done) and not metrics_all_ranks:
                     pkl = snap('network-snapshot-%06d.pkl' % (cur_nimg // 1000))
                     misc.save_pkl((G, D, Gs), pkl, reference_layout=True, build_module_src=module_src)
                     rng_state = torch.cuda.get_rng_state(device)    # the reference's metric ops carry their own seeds: evaluating a metric must not
                     metrics.run(pkl, run_dir=run_dir, data_dir=data_dir, dataset_args=ds_args, mirror_augment=mirror_augment,
                                 num_gpus=min([2, num_gpus]), tf_config=tf_config, device=device)                   # :519
                     torch.cuda.set_rng_state(rng_state, device)     # shift this rank's training draws (a run with metrics == a run without)
+            # World > 1: the snapshot's metrics spread over the ranks (fid*: every rank evaluates its rows, the statistics are merged on the
+            # device).  `snapshot_dir` is rank 0's run directory on every rank: the decision and the file name are the same everywhere.
+            if metrics_all_ranks and network_snapshot_ticks is not None and (cur_tick % max(network_snapshot_ticks, 1) == 0 or done):
+                pkl = os.path.join(snapshot_dir, 'network-snapshot-%06d.pkl' % (cur_nimg // 1000))
+                if rank == 0:
+                    misc.save_pkl((G, D, Gs), pkl, reference_layout=True, build_module_src=module_src)
+                torch.distributed.barrier()                         # the file is complete before any rank opens it
+                rng_state = torch.cuda.get_rng_state(device)
+                metrics.run(pkl, run_dir=run_dir if rank == 0 else None, data_dir=data_dir, dataset_args=ds_args, mirror_augment=mirror_augment,
+                            num_gpus=min([2, num_gpus]), tf_config=tf_config, device=device, process_group=torch.distributed.group.WORLD)
+                torch.cuda.set_rng_state(rng_state, device)
             if network_snapshot_ticks is not None and cur_tick > 0 and cur_tick % max(network_snapshot_ticks, 1) == 0 and use_graphs:
                 validate_graphs('tick %d' % cur_tick)      # long runs: the replays are re-checked at the network-snapshot cadence
                 autosummary_mod.flush()                    # the check's extra executions do not reach the next tick's statistics

@@ -1,11 +1,14 @@
 """Measured record of the FID statistics at the metric's own size (fid30k: 30 000 features x 2 048).
 
-    python tools/fid_bench.py [--n 30000] [--dim 2048] [--reps 3] [--runs 3] [--out FILE]
+    python tools/fid_bench.py [--n 30000] [--dim 2048] [--reps 3] [--runs 3] [--skip_kernels] [--skip_merge] [--skip_metric] [--out FILE]
 
 Part 1, the kernels (skipped on a tree that has no hip_ops.FeatureMoments): the device time (events on the stream) of all
 igan_moments_update launches over n resident feature rows in chunks of the metric's chunk_rows and of two other chunk sizes,
 the fp64 FLOP/s they amount to, the time of igan_moments_finalize, and the largest error of cov against a two-pass
 np.longdouble covariance on a sample of its rows (an extended-precision product of the whole matrix is hours of host time).
+
+Part 1b, the merge of two states (igan_moments_merge, what FeatureMoments.all_merge runs once per rank and feature set): time
+per call and bytes moved / time next to the HBM rate, cache resident and not.
 
 Part 2, the metric: `--runs` complete FID.run calls (reals and fakes, num_images = n, the metric's minibatch of 8) on a small
 32 x 32 generator with a synthetic device feature network -- a fixed random projection + ReLU to `dim` features -- with the wall
@@ -88,6 +91,50 @@ def kernel_part(a, emit):
                                  float(np.max(np.abs((mean.cpu().numpy().astype(np.longdouble) - mu).astype(np.float64))))))
 
 
+HBM_PEAK = 8.0e12          # bytes / s, MI355X data sheet (about 6.3e12 is what a plain copy reaches)
+
+
+def merge_part(a, emit):
+    """igan_moments_merge at F = dim: device time per call (events around `calls` launches, after a warm-up of the same
+    launches) and bytes moved / time.  Bytes: the elements on or above the diagonal of gram_a are read and written and those
+    of gram_b read, 3 * 8 * F (F + 1) / 2; sum and the shifts are 5 * 8 * F more.  Two settings: one pair of states over and
+    over (50 MB at F = 2048: it stays in the 256 MB last-level cache), and `pairs` different pairs in turn, more than the cache
+    holds, which is what one merge after a broadcast sees.  The time is stream time per call between two events: it includes
+    whatever gap the host leaves between launches, so it is an upper bound of the kernel's own time."""
+    import torch
+    from inclusivegan_amd import hip_ops
+    if not hasattr(hip_ops, 'moments_merge_raw'):
+        emit('merge: this tree has no hip_ops.moments_merge_raw: skipped')
+        return
+    dev = torch.device('cuda', 0)
+    F, pairs, calls = a.dim, 12, 480
+    nbytes = 3 * 8 * F * (F + 1) // 2 + 5 * 8 * F
+    gen = torch.Generator(device=dev).manual_seed(3)
+    states = [[torch.randn(F, device=dev, dtype=torch.float64, generator=gen), torch.randn(F, F, device=dev, dtype=torch.float64, generator=gen),
+               torch.randn(F, device=dev, dtype=torch.float64, generator=gen) * 1e-3] for _ in range(2 * pairs)]
+
+    def timed(order):
+        for i in order[:pairs]:
+            A, B = states[2 * i], states[2 * i + 1]
+            hip_ops.moments_merge_raw(A[0], A[1], A[2], B[0], B[1], B[2], 15000)
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for i in order:
+            A, B = states[2 * i], states[2 * i + 1]
+            hip_ops.moments_merge_raw(A[0], A[1], A[2], B[0], B[1], B[2], 15000)
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / len(order)
+
+    emit('igan_moments_merge F = %d: %.1f MB moved per call (upper triangles: gram_a read + written, gram_b read; sum, shifts)' % (F, nbytes / 1e6))
+    for name, order in (('one pair repeated (cache resident)', [0] * calls), ('%d pairs in turn (%.0f MB of triangles, past the last-level cache)' % (pairs, pairs * 2 * 8 * F * (F + 1) / 2 / 1e6), [i % pairs for i in range(calls)])):
+        ms = [timed(order) for _ in range(max(a.reps, 3))]
+        med = sorted(ms)[len(ms) // 2]
+        emit('  %s: median %.4f ms per call, min %.4f ms, of %d windows of %d calls  ->  %.2f TB/s = %.0f %% of the %.1f TB/s HBM data-sheet rate'
+             % (name, med, min(ms), len(ms), calls, nbytes / (med * 1e-3) / 1e12, 100.0 * nbytes / (med * 1e-3) / HBM_PEAK, HBM_PEAK / 1e12))
+
+
 class CopyCounter:
     """Counts device -> host transfers asked for through the tensor methods that make them."""
 
@@ -163,6 +210,7 @@ def main():
     ap.add_argument('--oracle_rows', type=int, default=12)
     ap.add_argument('--skip_kernels', action='store_true')
     ap.add_argument('--skip_metric', action='store_true')
+    ap.add_argument('--skip_merge', action='store_true')
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
     lines = []
@@ -174,6 +222,8 @@ def main():
     emit('fid_bench: %d x %d features' % (a.n, a.dim))
     if not a.skip_kernels:
         kernel_part(a, emit)
+    if not a.skip_merge:
+        merge_part(a, emit)
     if not a.skip_metric:
         metric_part(a, emit)
     if a.out:
