@@ -43,7 +43,7 @@ extern "C" {
  * igan_linear_svc_workspace_bytes, igan_linear_svc_grad, igan_linear_svc_hv, igan_linear_svc_linesearch, igan_linear_svc_predict,
  * igan_images_to_uint8, igan_images_from_uint8, igan_dense_small2_grouped, igan_dense_small_wgrad2_grouped, igan_rows_group_sum,
  * igan_scale_add, igan_kmeans_workspace_bytes, igan_kmeans_step, igan_moments_workspace_bytes, igan_moments_update, igan_moments_finalize,
- * igan_moments_merge). */
+ * igan_moments_merge, igan_class_hist_update, igan_prob_stats_update). */
 #define IGAN_ABI_VERSION 10
 
 typedef void* igan_stream_t; /* hipStream_t */
@@ -591,6 +591,33 @@ int igan_moments_finalize(igan_stream_t stream, const double* sum, const double*
                           double* mean /* [F] */, double* cov /* [F][F] */, long long n_total, int F);
 int igan_moments_merge(igan_stream_t stream, double* sum_a, double* gram_a, const double* shift_a /* [F] or NULL = 0 */,
                        const double* sum_b, const double* gram_b, const double* shift_b /* [F] or NULL = 0 */, long long n_b, int F);
+
+/* ------------------------------------------------------------------------
+ * Per-class statistics of classifier outputs, folded batch by batch on the device.  Added without a version bump: two more
+ * exports, no struct or signature changes.  Arguments are validated before anything touches a device: a null logits / counts
+ * / probs / psum / plogp, n < 1, K < 1, n * K * 4 at or above 2 GiB (longer row sets go in several calls), counts / psum /
+ * plogp not 8-byte aligned or an input not 4-byte aligned return IGAN_ERR_INVALID_ARGUMENT.  Inputs are dense row-major fp32
+ * and need 4-byte alignment ONLY: a row of an odd K starts anywhere, the kernels' 16-byte loads are declared 4-byte aligned.
+ *
+ * igan_class_hist_update replaces np.argmax(logits, axis=1) and the label array np.unique / np.histogram read on the host
+ * (reference: metrics/mode_counts.py:41-46, metrics/KL.py:41-49).  label[i] is np.argmax(logits[i]) exactly: the lowest index
+ * among equal maxima with -0.0 == +0.0, the index of the first NaN of a row that holds one, 0 for a row of -infinity; then
+ * counts[label[i]] += 1 into caller-zeroed running counts.  labels may be NULL.  One wavefront per row; a workgroup adds the
+ * multiplicity of each distinct label of its 16 rows with one 64-bit INTEGER atomic, so the counts do not depend on order.
+ *
+ * igan_prob_stats_update replaces the host activation block of the Inception Score (reference: metrics/inception_score.py:
+ * 43-54): it ACCUMULATES, in fp64 and as IEEE gives it,
+ *     psum[k] += sum_i (double)probs[i][k]          plogp[0] += sum_i sum_k (double)probs[i][k] * log((double)probs[i][k])
+ * from which a split's score is exp(plogp / n - sum_k m_k log m_k), m = psum / n.  A zero contributes 0 * -inf = NaN to
+ * plogp, a negative or NaN probability NaN (the reference's statement gives NaN for such a split too); psum of the other
+ * columns is untouched by it.  One thread owns a psum column and walks the rows in order; a row's plogp terms are summed per
+ * lane in ascending column order, over the lanes in a fixed tree, and one thread adds the row sums in row order -- no
+ * floating-point atomic: the bits are a function of (n, K) and the sequence of calls, and a repeated sequence gives
+ * identical bits.  The kernel knows nothing about splits: the caller cuts a batch at split boundaries. */
+int igan_class_hist_update(igan_stream_t stream, const float* logits /* [n][K] */, long long* counts /* [K], accumulated */,
+                           int* labels /* [n] or NULL */, int n, int K);
+int igan_prob_stats_update(igan_stream_t stream, const float* probs /* [n][K] */, double* psum /* [K], accumulated */,
+                           double* plogp /* [1], accumulated */, int n, int K);
 
 /* ------------------------------------------------------------------------
  * Perceptual path length (reference: metrics/perceptual_path_length.py; ppl_zfull .. ppl2_wend).  Added without a

@@ -2456,6 +2456,189 @@ class FeatureMoments:
         return self
 
 
+# ---- per-class statistics of classifier outputs (csrc/class_stats.hip; mode_counts / KL / IS) ------------------------------------
+def _require_rows_f32(name, X):
+    _require_cuda_f32(X)
+    if X.dim() != 2 or not X.is_contiguous():
+        raise ValueError('%s: the rows must be a contiguous [n, K] matrix (got %s, strides %s)' % (name, tuple(X.shape), tuple(X.stride())))
+
+
+def class_hist_update_raw(logits, counts, labels=None):
+    """counts [K] int64 += histogram of np.argmax(logits [n, K] fp32, axis=1) (igan_class_hist_update: first index among
+    equal maxima, first NaN of a row that holds one); labels [n] int32, when given, receives the arg-maxima.  In place, no
+    synchronisation; n * K * 4 below 2 GiB per call."""
+    lib = _abi.get_plugin()
+    _require_rows_f32('class_hist_update', logits)
+    for t, dtype, what in ((counts, torch.int64, 'counts: int64'), (labels, torch.int32, 'labels: int32')):
+        if t is None:
+            continue
+        if not t.is_cuda:
+            raise RuntimeError('inclusivegan_amd kernels need tensors on a ROCm device (got %s); there is no CPU path' % t.device)
+        if t.dtype != dtype or not t.is_contiguous() or t.device != logits.device:
+            raise TypeError('class_hist_update: %s, contiguous, on the device of the logits (got %s on %s)' % (what, t.dtype, t.device))
+    n, K = (int(v) for v in logits.shape)
+    if counts.numel() != K or (labels is not None and labels.numel() != n):
+        raise ValueError('class_hist_update: counts must be [K] and labels [n] for logits [n, K]')
+    _abi.check(lib.igan_class_hist_update(_stream(), _ptr(logits), _ptr(counts), _ptr(labels), n, K))
+
+
+def prob_stats_update_raw(probs, psum, plogp):
+    """psum [K] fp64 += column sums of probs [n, K] fp32, plogp [1] fp64 += sum of p log p over the block
+    (igan_prob_stats_update: fp64, fixed order, no floating-point atomic).  In place, no synchronisation."""
+    lib = _abi.get_plugin()
+    _require_rows_f32('prob_stats_update', probs)
+    _require_cuda_f64('prob_stats_update', psum, plogp)
+    n, K = (int(v) for v in probs.shape)
+    if psum.numel() != K or plogp.numel() != 1:
+        raise ValueError('prob_stats_update: psum must be [K] and plogp [1] for probs [n, K]')
+    if psum.device != probs.device or plogp.device != probs.device:
+        raise ValueError('prob_stats_update: the sums must live on the device of the rows')
+    _abi.check(lib.igan_prob_stats_update(_stream(), _ptr(probs), _ptr(psum), _ptr(plogp), n, K))
+
+
+def _device_rows(name, rows, K, dtypes):
+    if not torch.is_tensor(rows) or not rows.is_cuda:
+        raise RuntimeError('%s: the rows must be a tensor on a ROCm device; there is no CPU path' % name)
+    if rows.dim() != 2 or rows.shape[1] != K or rows.dtype not in dtypes:
+        raise ValueError('%s: the rows must be a %s [n, %d] tensor (got %s %s)' % (name, ' / '.join(str(d) for d in dtypes), K, rows.dtype, tuple(rows.shape)))
+    return rows.detach().contiguous()
+
+
+CLASS_STATS_MAX_BYTES = 2 ** 31 - 1        # one launch reads less than 2 GiB of rows
+
+
+class ClassHistogram:
+    """Histogram of the arg-max class of a stream of logit batches, kept on the device (np.bincount(np.argmax(rows, 1))).
+    update(logits [n, K] float32 on the device) folds a batch (igan_class_hist_update) and synchronises nothing; `counts` is
+    the int64 device tensor, to_host() the one device -> host copy, all_merge(group) the exact sum over the ranks."""
+
+    def __init__(self, K, device):
+        K = int(K)
+        if K < 1:
+            raise ValueError('ClassHistogram: K must be positive (got %d)' % K)
+        self.K, self.device = K, torch.device(device)
+        self.count = 0
+        self.counts = torch.zeros(K, device=self.device, dtype=torch.int64)
+
+    def update(self, logits, return_labels=False):
+        logits = _device_rows('ClassHistogram.update', logits, self.K, (torch.float32,))
+        n = int(logits.shape[0])
+        labels = torch.empty(n, device=logits.device, dtype=torch.int32) if return_labels else None
+        step = max(1, CLASS_STATS_MAX_BYTES // (4 * self.K))
+        for r0 in range(0, n, step):
+            class_hist_update_raw(logits[r0:r0 + step], self.counts, None if labels is None else labels[r0:r0 + step])
+        self.count += n
+        return labels
+
+    def merge(self, other):
+        if not isinstance(other, ClassHistogram) or other is self or other.K != self.K or other.device != self.device:
+            raise ValueError('ClassHistogram.merge: the other side must be another ClassHistogram of the same K on the same device')
+        self.counts += other.counts
+        self.count += other.count
+        return self
+
+    def all_merge(self, group=None):
+        """Every rank of `group` ends with the sum of all ranks' counts: one all_reduce(SUM) of the int64 device tensor (the
+        route training_loop.combine_best_ takes), exact whatever the order.  A collective."""
+        both = torch.cat([self.counts, torch.tensor([self.count], device=self.device, dtype=torch.int64)])
+        torch.distributed.all_reduce(both, op=torch.distributed.ReduceOp.SUM, group=group)
+        self.counts = both[:self.K].clone()
+        self.count = int(both[self.K].item())
+        return self
+
+    def to_host(self):
+        return self.counts.cpu().numpy()
+
+
+def split_bounds(num_images, num_splits):
+    """(begin, end) of every split of metrics/inception_score.py:50-51: split s holds rows s N // S .. (s + 1) N // S."""
+    num_images, num_splits = int(num_images), int(num_splits)
+    if num_images < 0 or num_splits < 1:
+        raise ValueError('split_bounds: need num_images >= 0 and num_splits >= 1')
+    return [(s * num_images // num_splits, (s + 1) * num_images // num_splits) for s in range(num_splits)]
+
+
+def scores_from_sums(n, psum, plogp):
+    """Inception Score of every split from its sums, fp64 on the host: with m = psum_s / n_s,
+        exp(plogp_s / n_s - sum_k m_k log m_k)
+    which is the reference's exp(mean_i sum_k p_ik (log p_ik - log m_k)) because mean_i sum_k p_ik log m_k = sum_k m_k log m_k.
+    n [S], psum [S, K], plogp [S]; an empty split gives NaN, as the mean of no rows does."""
+    n = np.asarray(n, dtype=np.float64).reshape(-1)
+    psum = np.asarray(psum, dtype=np.float64).reshape(n.shape[0], -1)
+    plogp = np.asarray(plogp, dtype=np.float64).reshape(-1)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        m = psum / n[:, None]
+        return np.exp(plogp / n - np.sum(m * np.log(m), axis=1))
+
+
+class SplitProbStats:
+    """The sums behind the Inception Score of `num_splits` splits of `num_images` probability rows, kept on the device.
+    update(probs [b, K] float32 on the device, first_global_row) cuts the batch at the split boundaries on the host and
+    launches igan_prob_stats_update once per piece into that split's (n_s, psum_s, plogp_s); rows may come in any order and
+    from any rank, each exactly once.  all_merge(group) leaves every rank with the same bits, scores() is the one device ->
+    host copy."""
+
+    def __init__(self, K, num_images, num_splits, device):
+        K = int(K)
+        if K < 1:
+            raise ValueError('SplitProbStats: K must be positive (got %d)' % K)
+        self.K, self.num_images, self.num_splits, self.device = K, int(num_images), int(num_splits), torch.device(device)
+        self.bounds = split_bounds(num_images, num_splits)
+        self.n = [0] * self.num_splits
+        self.psum = torch.zeros((self.num_splits, K), device=self.device, dtype=torch.float64)
+        self.plogp = torch.zeros(self.num_splits, device=self.device, dtype=torch.float64)
+
+    def update(self, probs, first_global_row):
+        probs = _device_rows('SplitProbStats.update', probs, self.K, (torch.float32,))
+        first, b = int(first_global_row), int(probs.shape[0])
+        if first < 0 or first + b > self.num_images:
+            raise ValueError('SplitProbStats.update: rows [%d, %d) are outside the %d images' % (first, first + b, self.num_images))
+        step = max(1, CLASS_STATS_MAX_BYTES // (4 * self.K))
+        for s, (begin, end) in enumerate(self.bounds):
+            lo, hi = max(begin, first), min(end, first + b)
+            for r0 in range(lo, hi, step):
+                r1 = min(r0 + step, hi)
+                prob_stats_update_raw(probs[r0 - first:r1 - first], self.psum[s], self.plogp[s:s + 1])
+                self.n[s] += r1 - r0
+
+    def _state(self):
+        return torch.cat([torch.tensor(self.n, device=self.device, dtype=torch.float64), self.plogp, self.psum.reshape(-1)])
+
+    def _adopt(self, state):
+        S = self.num_splits
+        self.n = [int(v) for v in state[:S].cpu().numpy()]
+        self.plogp = state[S:2 * S].clone()
+        self.psum = state[2 * S:].reshape(S, self.K).clone()
+
+    def merge(self, other):
+        if (not isinstance(other, SplitProbStats) or other is self or other.device != self.device
+                or (other.K, other.num_images, other.num_splits) != (self.K, self.num_images, self.num_splits)):
+            raise ValueError('SplitProbStats.merge: the other side must be another SplitProbStats of the same K, images, splits and device')
+        self._adopt(self._state() + other._state())
+        return self
+
+    def all_merge(self, group=None):
+        """Rank by rank, the owner broadcasts (n, plogp, psum) as one fp64 vector and every rank adds it, in rank order, to a
+        sum that starts at zero: all ranks end with the same bits, like FeatureMoments.all_merge.  A collective; it
+        synchronises (the counts are read on the host)."""
+        dist = torch.distributed
+        world, rank = dist.get_world_size(group), dist.get_rank(group)
+        mine = self._state()
+        total = torch.zeros_like(mine)
+        for r in range(world):
+            src = r if group is None else dist.get_global_rank(group, r)
+            buf = mine.clone() if r == rank else torch.empty_like(mine)
+            dist.broadcast(buf, src, group=group)
+            total += buf
+        self._adopt(total)
+        return self
+
+    def scores(self):
+        S = self.num_splits
+        state = self._state().cpu().numpy()
+        return scores_from_sums(state[:S], state[2 * S:].reshape(S, self.K), state[S:2 * S])
+
+
 # ----------------------------------------------------------------------------
 # perceptual path length
 

@@ -4,7 +4,15 @@
 
 The Inception-v3 softmax network of the reference (metrics/inception_v3_softmax.pkl) is not available; `IS` takes
 `classify_fn(uint8 images [n, C, H, W] on the device) -> softmax probabilities [n, K]` instead, like `FID`'s `feature_fn`.
-The statistic on top of it is host NumPy, value for value."""
+Probabilities that come back as device tensors stay on the device: every minibatch is cast to float32 as the host path
+casts it and folded into a `hip_ops.SplitProbStats` (csrc/class_stats.hip: per split the row count, the fp64 column sums and the
+fp64 sum of p log p, in a fixed order), and a split's score is  exp(plogp / n - sum_k m_k log m_k),  m = psum / n  -- the
+reference's statement with the mean over the images taken first.  NumPy / CPU results are collected on the host and go
+through the reference's statement, value for value.
+
+Under a process group (`run(..., process_group=)`) the images are dealt to the ranks as FID deals them
+(`MetricBase._fold_shard_fakes`); a row's split is decided by its GLOBAL index, every rank folds its rows,
+`SplitProbStats.all_merge` leaves every rank with the same bits and rank 0 reports.  Host results are REFUSED under a group."""
 import numpy as np
 import torch
 
@@ -25,6 +33,8 @@ def inception_score_splits(activations, num_splits):
 
 
 class IS(metric_base.MetricBase):
+    multi_rank = True
+
     def __init__(self, num_images, num_splits, minibatch_per_gpu, classify_fn=None, **kwargs):
         super().__init__(**kwargs)
         self.num_images = num_images
@@ -32,21 +42,64 @@ class IS(metric_base.MetricBase):
         self.minibatch_per_gpu = minibatch_per_gpu
         self.classify_fn = classify_fn
 
+    def _shard_stats(self, Gs, Gs_kwargs, rank, world):
+        """hip_ops.SplitProbStats of the fakes rank `rank` of `world` owns, or None when it owns none -- a function of its
+        arguments alone (MetricBase._fold_shard_fakes), so one process can rebuild every rank's state."""
+        from .. import hip_ops
+        state = []
+
+        def fold(begin, end, images):
+            probs = self.classify_fn(images)
+            if not (torch.is_tensor(probs) and probs.is_cuda):
+                raise RuntimeError('IS under a process group: classify_fn must return device tensors; host (NumPy / CPU) results are '
+                                   'evaluated by one process only (run without process_group)')
+            if not state:
+                state.append(hip_ops.SplitProbStats(probs.shape[1], self.num_images, self.num_splits, probs.device))
+            state[0].update(probs.detach().to(torch.float32), begin)
+
+        self._fold_shard_fakes(Gs, Gs_kwargs, rank, world, fold)
+        return state[0] if state else None
+
+    def _evaluate_sharded(self, Gs, Gs_kwargs):
+        from .. import hip_ops
+        group = self._process_group
+        rank, world = torch.distributed.get_rank(group), torch.distributed.get_world_size(group)
+        stats = self._shard_stats(Gs, Gs_kwargs, rank, world)
+        K = self._agree_on_width(stats.K if stats is not None else 0, Gs.device, 'probability')
+        if stats is None:
+            stats = hip_ops.SplitProbStats(K, self.num_images, self.num_splits, Gs.device)
+        scores = stats.all_merge(group).scores()
+        if rank == 0:
+            self._report_result(np.mean(scores), suffix='_mean')
+            self._report_result(np.std(scores), suffix='_std')
+
     def _evaluate(self, Gs, Gs_kwargs, num_gpus):
         if self.classify_fn is None:
             raise RuntimeError('IS needs classify_fn: the reference\'s metrics/inception_v3_softmax.pkl is not available in this tree')
+        if self._process_group is not None:
+            return self._evaluate_sharded(Gs, Gs_kwargs)
         minibatch_size = num_gpus * self.minibatch_per_gpu
-        activations = None
+        activations = stats = None
 
         # Calculate activations for fakes.
         for begin in range(0, self.num_images, minibatch_size):
             end = min(begin + minibatch_size, self.num_images)
-            probs = torch.as_tensor(self.classify_fn(self._generate(Gs, minibatch_size, Gs_kwargs))).detach().to('cpu', torch.float32).numpy()
+            probs = self.classify_fn(self._generate(Gs, minibatch_size, Gs_kwargs))
+            on_device = torch.is_tensor(probs) and probs.is_cuda
+            if begin and on_device != (stats is not None):
+                raise RuntimeError('IS: classify_fn must return device tensors for every minibatch or for none')
+            if on_device:
+                if stats is None:
+                    from .. import hip_ops
+                    stats = hip_ops.SplitProbStats(probs.shape[1], self.num_images, self.num_splits, probs.device)
+                stats.update(probs.detach().to(torch.float32)[:end - begin], begin)
+                continue
+            probs = torch.as_tensor(probs).detach().to('cpu', torch.float32).numpy()
             if activations is None:
                 activations = np.empty([self.num_images, probs.shape[1]], dtype=np.float32)
             activations[begin:end] = probs[:end - begin]
 
         # Calculate IS.
-        scores = inception_score_splits(activations, self.num_splits)
+        scores = stats.scores() if stats is not None else inception_score_splits(activations, self.num_splits)
         self._report_result(np.mean(scores), suffix='_mean')
         self._report_result(np.std(scores), suffix='_std')

@@ -167,6 +167,34 @@ class MetricBase:
         images = Gs.get_output_for(latents, labels, **Gs_kwargs)
         return convert_images_to_uint8(images) if as_uint8 else images
 
+    # ---- under a process group (metrics with num_images / minibatch_per_gpu) -------------------------------------------------
+    def _fold_shard_fakes(self, Gs, Gs_kwargs, rank, world, fold, as_uint8=True):
+        """`fold(begin, end, images)` for the fakes of every global minibatch that rank `rank` of `world` owns, the way
+        FID._shard_moments deals them: a global minibatch is world x minibatch_per_gpu images, the rank owns rows [rank mb,
+        (rank + 1) mb) of it (frechet_inception_distance.shard_slices; the last slice is cut at num_images and may be empty),
+        labels are drawn for the global minibatch and sliced, latents and noise come from a private device generator seeded
+        SHARD_SEED + rank.  A function of (rank, world) and the arguments alone: one process can replay every rank."""
+        from .frechet_inception_distance import SHARD_SEED, shard_slices
+        mb = self.minibatch_per_gpu
+        self._label_rng = None
+        with tfutil.use_random(tfutil.SeededRandom(Gs.device, SHARD_SEED + rank)):
+            for begin, end in shard_slices(self.num_images, mb, rank, world):
+                labels = self._get_random_labels(world * mb, Gs)[rank * mb:(rank + 1) * mb]
+                if end > begin:
+                    fold(begin, end, self._generate(Gs, mb, Gs_kwargs, as_uint8=as_uint8, labels=labels)[:end - begin])
+
+    def _agree_on_width(self, K, device, what):
+        """The one row width K of all ranks of the group; a rank without rows passes 0 and learns it here (all-reduce MAX).
+        Ranks that disagree, or a group without a single row, raise ValueError on every rank."""
+        both = torch.tensor([int(K), -int(K) if K else -2 ** 62], device=device, dtype=torch.int64)
+        torch.distributed.all_reduce(both, op=torch.distributed.ReduceOp.MAX, group=self._process_group)
+        widest, narrowest = int(both[0].item()), -int(both[1].item())
+        if widest == 0:
+            raise ValueError('%s: no rank holds a %s row' % (type(self).__name__, what))
+        if narrowest != widest:
+            raise ValueError('%s: the ranks disagree on the width of a %s row (%d .. %d columns)' % (type(self).__name__, what, narrowest, widest))
+        return widest
+
 
 def _retarget(kwargs):
     """The reference names its metrics `metrics.<module>.<Class>`; the same classes live under this package."""

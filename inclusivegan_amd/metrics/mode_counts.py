@@ -1,6 +1,17 @@
 """Number of Stacked-MNIST modes covered by the generator (reference: metrics/mode_counts.py:20-49): classify `num_images`
 fakes into the 1000 digit triples and count the distinct classes hit.  The classifier (metrics/stacked_mnist_classifier.pkl
-in the reference) is injected: `classify_fn(float images [n, C, H, W] in [-1, 1]) -> logits [n, K]`."""
+in the reference) is injected: `classify_fn(float images [n, C, H, W] in [-1, 1]) -> logits [n, K]`.
+
+Logits that come back as float32 device tensors stay on the device: every minibatch is folded into a
+`hip_ops.ClassHistogram` (csrc/class_stats.hip: np.argmax per row, 64-bit integer counts) and the K counts are the one device
+-> host copy; the mode count and KL.py's divergence are functions of the counts (`count_modes_from_counts`,
+`KL.kl_from_counts`).  Any other result -- NumPy, a CPU tensor, another dtype -- goes through np.argmax on the host, the
+reference's statements.
+
+Under a process group (`run(..., process_group=)`) the images are dealt to the ranks as FID deals them
+(`MetricBase._fold_shard_fakes`), every rank folds its rows into its own histogram, one all_reduce(SUM) of the int64 counts
+gives every rank the exact total and rank 0 reports.  Host results are REFUSED under a group: they are evaluated by one
+process."""
 import numpy as np
 
 from . import metric_base
@@ -26,7 +37,85 @@ def count_modes(labels_all):
     return len(np.unique(labels_all))
 
 
+def counts_of_labels(labels_all, num_classes):
+    """The class histogram KL.kl_to_uniform takes of the labels (np.histogram over the bins 0 .. K)."""
+    return np.histogram(labels_all, bins=np.arange(num_classes + 1))[0]
+
+
+def count_modes_from_counts(counts):
+    return int(np.count_nonzero(counts))
+
+
+def _on_device_f32(logits):
+    import torch
+    return torch.is_tensor(logits) and logits.is_cuda and logits.dtype == torch.float32
+
+
+def class_statistics(metric, Gs, Gs_kwargs, num_gpus):
+    """One process, the draws of `predicted_labels`: float32 device logits are folded on the device -> (counts [K] NumPy
+    integers, None, K); anything else is labelled on the host as there -> (None, labels_all, K)."""
+    import torch
+    from .. import hip_ops
+    if metric.classify_fn is None:
+        raise RuntimeError('%s needs classify_fn: the reference\'s metrics/stacked_mnist_classifier.pkl is not available in this tree' % metric.name)
+    minibatch_size = num_gpus * metric.minibatch_per_gpu
+    hist = labels_all = num_classes = None
+    for begin in range(0, metric.num_images, minibatch_size):
+        end = min(begin + minibatch_size, metric.num_images)
+        logits = metric.classify_fn(metric._generate(Gs, minibatch_size, Gs_kwargs, as_uint8=False))     # the classifier sees G's float output (:39-40)
+        on_device = _on_device_f32(logits)
+        if begin and on_device != (hist is not None):
+            raise RuntimeError('%s: classify_fn must return float32 device tensors for every minibatch or for none' % metric.name)
+        if on_device:
+            if hist is None:
+                hist = hip_ops.ClassHistogram(logits.shape[1], logits.device)
+            hist.update(logits[:end - begin])
+        else:
+            logits = logits.detach().cpu().numpy() if torch.is_tensor(logits) else np.asarray(logits)
+            if labels_all is None:
+                labels_all = np.empty([metric.num_images], dtype=np.float32)
+            num_classes = logits.shape[1]
+            labels_all[begin:end] = np.argmax(logits, axis=1)[:end - begin]
+    return (hist.to_host(), None, hist.K) if hist is not None else (None, labels_all, num_classes)
+
+
+def shard_histogram(metric, Gs, Gs_kwargs, rank, world):
+    """hip_ops.ClassHistogram of the fakes rank `rank` of `world` owns, or None when it owns none -- a function of its
+    arguments alone (MetricBase._fold_shard_fakes), so one process can rebuild every rank's state."""
+    from .. import hip_ops
+    if metric.classify_fn is None:
+        raise RuntimeError('%s needs classify_fn: the reference\'s metrics/stacked_mnist_classifier.pkl is not available in this tree' % metric.name)
+    state = []
+
+    def fold(begin, end, images):
+        logits = metric.classify_fn(images)
+        if not _on_device_f32(logits):
+            raise RuntimeError('%s under a process group: classify_fn must return float32 device tensors; host (NumPy / CPU) results are '
+                               'evaluated by one process only (run without process_group)' % type(metric).__name__)
+        if not state:
+            state.append(hip_ops.ClassHistogram(logits.shape[1], logits.device))
+        state[0].update(logits)
+
+    metric._fold_shard_fakes(Gs, Gs_kwargs, rank, world, fold, as_uint8=False)
+    return state[0] if state else None
+
+
+def merged_class_counts(metric, Gs, Gs_kwargs):
+    """Under metric._process_group: this rank's shard folded, then the total over all ranks (the same integers on every rank)."""
+    import torch
+    from .. import hip_ops
+    group = metric._process_group
+    rank, world = torch.distributed.get_rank(group), torch.distributed.get_world_size(group)
+    hist = shard_histogram(metric, Gs, Gs_kwargs, rank, world)
+    K = metric._agree_on_width(hist.K if hist is not None else 0, Gs.device, 'logit')
+    if hist is None:
+        hist = hip_ops.ClassHistogram(K, Gs.device)
+    return hist.all_merge(group).to_host()
+
+
 class mode_counts(metric_base.MetricBase):
+    multi_rank = True
+
     def __init__(self, num_images, minibatch_per_gpu, classify_fn=None, **kwargs):
         super().__init__(**kwargs)
         self.num_images = num_images
@@ -34,5 +123,11 @@ class mode_counts(metric_base.MetricBase):
         self.classify_fn = classify_fn
 
     def _evaluate(self, Gs, Gs_kwargs, num_gpus):
-        labels_all, _ = predicted_labels(self, Gs, Gs_kwargs, num_gpus)
-        self._report_result(count_modes(labels_all))
+        import torch
+        if self._process_group is not None:
+            counts = merged_class_counts(self, Gs, Gs_kwargs)
+            if torch.distributed.get_rank(self._process_group) == 0:
+                self._report_result(count_modes_from_counts(counts))
+            return
+        counts, labels_all, _ = class_statistics(self, Gs, Gs_kwargs, num_gpus)
+        self._report_result(count_modes_from_counts(counts) if counts is not None else count_modes(labels_all))
