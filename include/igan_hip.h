@@ -43,7 +43,7 @@ extern "C" {
  * igan_linear_svc_workspace_bytes, igan_linear_svc_grad, igan_linear_svc_hv, igan_linear_svc_linesearch, igan_linear_svc_predict,
  * igan_images_to_uint8, igan_images_from_uint8, igan_dense_small2_grouped, igan_dense_small_wgrad2_grouped, igan_rows_group_sum,
  * igan_scale_add, igan_kmeans_workspace_bytes, igan_kmeans_step, igan_moments_workspace_bytes, igan_moments_update, igan_moments_finalize,
- * igan_moments_merge, igan_class_hist_update, igan_prob_stats_update). */
+ * igan_moments_merge, igan_class_hist_update, igan_prob_stats_update, igan_nnk_update). */
 #define IGAN_ABI_VERSION 10
 
 typedef void* igan_stream_t; /* hipStream_t */
@@ -496,6 +496,26 @@ int igan_nn1_update(igan_stream_t stream, const float* query, const float* qnorm
                     const float* cand, const float* cnorm, double* best_d2, int* best_idx,
                     float* dots /* caller workspace, nq*nc floats */,
                     int nq, int nc, int dim, int idx_base);
+
+/* ------------------------------------------------------------------------
+ * Exact streaming k-nearest-neighbours with indices (replaces dci_query(num_neighbours = k) as the exclusive IMLE
+ * assignment uses it, training/training_loop.py:382-396).  After any sequence of calls
+ *   (best_d2[q][0..k), best_idx[q][0..k)) = the k lexicographically smallest pairs (|query_q - cand_c|^2, idx_base + c)
+ * over all candidates fed so far, ascending, ties in distance to the lower index, with the squared distance of
+ * igan_nn1_update (a direct difference in fp64); the fp32 MFMA product screens with the same error interval and every
+ * pair it cannot rule out is measured exactly.  Initialise best_d2 to +infinity and best_idx to INT32_MAX.  The state is a
+ * function of the set of (row, index) pairs fed -- not of the order or the boundaries of the batches, bits of the distances
+ * included -- and with k = 1 it is igan_nn1_update's, bit for bit.  A candidate whose exact distance is not finite never
+ * enters; with fewer than k finite candidates the trailing slots stay (+infinity, INT32_MAX).
+ * 1 <= k <= 16 (IGAN_ERR_UNSUPPORTED beyond); non-null buffers, positive sizes, idx_base >= 0 and idx_base + nc <=
+ * INT32_MAX, the operand limits of igan_conv2d (IGAN_ERR_INVALID_ARGUMENT).  Arguments are validated before anything
+ * touches a device.
+ */
+int igan_nnk_update(igan_stream_t stream, const float* query, const float* qnorm,
+                    const float* cand, const float* cnorm,
+                    double* best_d2 /* [nq][k] */, int* best_idx /* [nq][k] */,
+                    float* dots /* caller workspace, nq*nc floats */,
+                    int nq, int nc, int dim, int k, int idx_base);
 
 /* ------------------------------------------------------------------------
  * Exact k-NN manifold search for the precision / recall metric (reference: metrics/precision_recall.py).

@@ -202,6 +202,7 @@ SIGNATURES = {
     'igan_mbstd_bwd': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I]),
     'igan_row_sqnorm': (_I, [_P, _P, _P, _I, _I]),
     'igan_nn1_update': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I]),
+    'igan_nnk_update': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I]),
     'igan_knn_radius_update': (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I]),
     'igan_manifold_member_update': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I]),
     'igan_kmeans_workspace_bytes': (_SZ, [_I, _I, _I]),

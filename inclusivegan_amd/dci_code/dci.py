@@ -14,8 +14,9 @@ answer.  Extension: `add` / `query` also accept device tensors, so candidates ge
 never visit the host (the reference materialises a 118 GB fp64 array, training_loop.py:358).
 
 `num_neighbours == 1` (the default, non-exclusive IMLE assignment, training_loop.py:398) runs entirely in the streaming
-HIP kernel; `num_neighbours > 1` (the exclusive variant, :382-396) screens with the same MFMA products and re-ranks a
-short list exactly with torch ops.
+HIP kernel, and so does `2 <= num_neighbours <= hip_ops.NNK_MAX_K` (the exclusive variant, :382-396): the same search keeping
+the k smallest (distance, index) pairs per query (`query_device_nnk`, csrc/nnk.hip).  Beyond NNK_MAX_K neighbours
+`query_device_k` screens with the same MFMA products and re-ranks a short list exactly with torch ops.
 """
 import numpy as np
 import torch
@@ -113,7 +114,10 @@ class DCI(object):
             idx = idx.cpu().numpy().astype(np.int32)
             dist = dist.cpu().numpy().astype(np.float64)
             return [idx[i:i + 1] for i in range(idx.shape[0])], [dist[i:i + 1] for i in range(dist.shape[0])]
-        idx, dist = self.query_device_k(q, num_neighbours)
+        if 2 <= num_neighbours <= hip_ops.NNK_MAX_K:
+            idx, dist = self.query_device_nnk(q, num_neighbours)
+        else:
+            idx, dist = self.query_device_k(q, num_neighbours)
         idx = idx.cpu().numpy().astype(np.int32)
         dist = dist.cpu().numpy().astype(np.float64)
         return [idx[i] for i in range(idx.shape[0])], [dist[i] for i in range(dist.shape[0])]
@@ -128,6 +132,21 @@ class DCI(object):
             qn = hip_ops.row_sqnorm_raw(qs)
             for c0 in range(0, n, self.cand_chunk):
                 hip_ops.nn1_update_raw(qs, qn, self._data[c0:c0 + self.cand_chunk], self._norms[c0:c0 + self.cand_chunk],
+                                       best_d2[q0:q0 + self.query_chunk], best_idx[q0:q0 + self.query_chunk], c0)
+        return unpack_best(best_d2, best_idx)
+
+    def query_device_nnk(self, q, k):
+        """q: device fp32 [nq, dim], 1 <= k <= hip_ops.NNK_MAX_K -> (int64 idx [nq, k], fp64 Euclidean dist [nq, k]) on the device,
+        ascending, ties to the lower index: the streaming search of `query_device` keeping k (distance, index) pairs per query.
+        With fewer than k candidates at a finite distance the trailing slots are (INT32_MAX, +inf)."""
+        nq = int(q.shape[0])
+        best_d2, best_idx = hip_ops.nnk_state(nq, k, self.device)
+        n = self.num_points
+        for q0 in range(0, nq, self.query_chunk):
+            qs = q[q0:q0 + self.query_chunk]
+            qn = hip_ops.row_sqnorm_raw(qs)
+            for c0 in range(0, n, self.cand_chunk):
+                hip_ops.nnk_update_raw(qs, qn, self._data[c0:c0 + self.cand_chunk], self._norms[c0:c0 + self.cand_chunk],
                                        best_d2[q0:q0 + self.query_chunk], best_idx[q0:q0 + self.query_chunk], c0)
         return unpack_best(best_d2, best_idx)
 

@@ -2178,6 +2178,38 @@ def nn1_update_raw(query, qnorm, cand, cnorm, best_d2, best_idx, idx_base):
                                    nq, nc, dim, idx_base))
 
 
+NNK_MAX_K = 16      # igan_nnk_update: the k (distance, index) pairs of a query live in registers
+
+
+def nnk_state(nq, k, device):
+    """Running state of igan_nnk_update for nq queries: the k smallest (squared distance, candidate index) pairs,
+    (fp64 [nq, k] = +inf, int32 [nq, k] = INT32_MAX)."""
+    if not 1 <= int(k) <= NNK_MAX_K:
+        raise ValueError('nnk_state: k must be in [1, %d]' % NNK_MAX_K)
+    return (torch.full((nq, int(k)), float('inf'), device=device, dtype=torch.float64),
+            torch.full((nq, int(k)), 2 ** 31 - 1, device=device, dtype=torch.int32))
+
+
+def nnk_update_raw(query, qnorm, cand, cnorm, best_d2, best_idx, idx_base):
+    """Fold one candidate batch into the running k smallest exact (squared distance, index) pairs (best_d2 fp64 [nq, k],
+    best_idx int32 [nq, k], ascending, ties to the lower index; contiguous views)."""
+    lib = _abi.get_plugin()
+    _require_cuda_f32(query, qnorm, cand, cnorm)
+    if best_d2.dtype != torch.float64 or not best_d2.is_contiguous() or best_d2.dim() != 2:
+        raise TypeError('nnk_update: best_d2 must be contiguous float64 [nq, k]')
+    if best_idx.dtype != torch.int32 or not best_idx.is_contiguous() or best_idx.dim() != 2:
+        raise TypeError('nnk_update: best_idx must be contiguous int32 [nq, k]')
+    query = query.contiguous()
+    cand = cand.contiguous()
+    nq, dim = query.shape
+    nc = cand.shape[0]
+    if best_d2.shape[0] != nq or best_idx.shape != best_d2.shape or cand.shape[1] != dim or qnorm.numel() != nq or cnorm.numel() != nc:
+        raise ValueError('nnk_update: shapes of query, cand, norms, best_d2 and best_idx do not agree')
+    dots = torch.empty((nq, nc), device=query.device, dtype=torch.float32)
+    _abi.check(lib.igan_nnk_update(_stream(), _ptr(query), _ptr(qnorm.contiguous()), _ptr(cand), _ptr(cnorm.contiguous()), _ptr(best_d2), _ptr(best_idx),
+                                   _ptr(dots), nq, nc, dim, best_d2.shape[1], idx_base))
+
+
 def knn_radius_state(nq, kcap, device):
     """Running state of igan_knn_radius_update for nq queries: the kcap smallest exact squared distances, fp64 [nq, kcap] = +inf."""
     if not 1 <= int(kcap) <= 16:

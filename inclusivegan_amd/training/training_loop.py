@@ -130,6 +130,10 @@ def training_schedule(
 
 #----------------------------------------------------------------------------
 
+# A/B switch, read once at import: IGAN_NNK_STREAM=0 puts the exclusive assignment back on the resident-candidates path.
+NNK_STREAM = os.environ.get('IGAN_NNK_STREAM', '1') != '0'
+
+
 def _dist_info():
     if torch.distributed.is_available() and torch.distributed.is_initialized():
         return torch.distributed.get_rank(), torch.distributed.get_world_size()
@@ -167,6 +171,15 @@ def exclusive_assignment(knn_idx, knn_dist):
     return idx_out, dist_out
 
 
+def merge_knn_lists(all_i, all_d, k):
+    """The ranks' k-NN lists (each int64 idx [data_size, k], fp64 dist [data_size, k]; "no candidate" = (INT32_MAX, +inf)) -> the k
+    nearest over all shards, ascending, ties to the lower index: two stable sorts and the first k."""
+    gi, ld = torch.cat(list(all_i), dim=1), torch.cat(list(all_d), dim=1)
+    o = torch.argsort(gi, dim=1, stable=True); gi, ld = torch.gather(gi, 1, o), torch.gather(ld, 1, o)
+    o = torch.argsort(ld, dim=1, stable=True); gi, ld = torch.gather(gi, 1, o)[:, :k], torch.gather(ld, 1, o)[:, :k]
+    return gi, ld
+
+
 def imle_refresh(G, training_set_rec, latent_candidates, label_candidates, data_size, minibatch_size, candidate_batch_size,
                  drange_net, device, rank=0, world=1, query_chunk=8192, infer_minibatch=None, projector=None, exclusive_k=0, cand_pack=4096):
     """IMLE assignment (:357-406, non-exclusive): every real image (dataset order, [-1,1] range, flattened CHW;
@@ -175,7 +188,33 @@ def imle_refresh(G, training_set_rec, latent_candidates, label_candidates, data_
     mode, random noise -- `G.run(..., is_validation=True)`, :361) and folded, a pack of `cand_pack` at a time, into a running
     per-real minimum; rank r handles packs r, r+world, ... and the minima are combined across ranks.  The reals are pulled from
     `training_set_rec` exactly as the reference's query loop does (2 * minibatch_size per call, data_size in all, :374-403).
+    With `exclusive_k` > 1 (:382-396) every real gets its exclusive_k nearest candidates instead, merged over the ranks, and the
+    reference's greedy pick runs on the host (`exclusive_assignment`).
     Returns (nearest_indices int64 [data_size], dists float64 [data_size]) as NumPy."""
+    found = imle_search(G, training_set_rec, latent_candidates, label_candidates, data_size, minibatch_size, candidate_batch_size,
+                        drange_net, device, rank=rank, world=world, query_chunk=query_chunk, infer_minibatch=infer_minibatch,
+                        projector=projector, exclusive_k=exclusive_k, cand_pack=cand_pack)
+    if exclusive_k > 1:
+        gi, ld = found
+        if world > 1:       # a few megabytes: every rank's lists to every rank, then the same merge and pick everywhere
+            all_i = [torch.empty_like(gi) for _ in range(world)]; all_d = [torch.empty_like(ld) for _ in range(world)]
+            torch.distributed.all_gather(all_i, gi); torch.distributed.all_gather(all_d, ld)
+            gi, ld = merge_knn_lists(all_i, all_d, int(exclusive_k))
+        return exclusive_assignment(gi.cpu().numpy(), ld.cpu().numpy())
+    best_d2, best_idx = found
+    combine_best_(best_d2, best_idx, world)
+    idx, dist = unpack_best(best_d2, best_idx)
+    return idx.cpu().numpy(), dist.cpu().numpy().astype(np.float64)
+
+
+def imle_search(G, training_set_rec, latent_candidates, label_candidates, data_size, minibatch_size, candidate_batch_size,
+                drange_net, device, rank=0, world=1, query_chunk=8192, infer_minibatch=None, projector=None, exclusive_k=0, cand_pack=4096):
+    """The device work of `imle_refresh` on THIS rank's candidate packs (rank, rank + world, ...), before anything is merged over
+    the ranks: the running minimum (best_d2 fp64 [data_size], best_idx int32 [data_size]) -- or, with `exclusive_k` > 1, the
+    k-NN lists (int64 idx [data_size, k], fp64 Euclidean dist [data_size, k]; (INT32_MAX, +inf) where the shard ran out).
+    For 2 <= exclusive_k <= hip_ops.NNK_MAX_K the lists are streamed like the minimum: every pack is folded into k running
+    (distance, index) pairs per real (igan_nnk_update) and thrown away.  Beyond NNK_MAX_K, or with IGAN_NNK_STREAM=0, this rank's
+    candidates stay resident on the device and DCI.query_device_k searches them at the end."""
     num_cand = latent_candidates.shape[0]
     dim = int(np.prod(training_set_rec.shape))
     pdim = dim if projector is None else int(projector.shape[1])
@@ -193,8 +232,13 @@ def imle_refresh(G, training_set_rec, latent_candidates, label_candidates, data_
         reals[i:i + r.shape[0]] = r if projector is None else hip_ops.matmul(r, projector)
         i += r.shape[0]
     rnorm = hip_ops.row_sqnorm_raw(reals)
-    best_d2, best_idx = hip_ops.nn1_state(data_size, device)
-    resident = [] if exclusive_k > 1 else None      # exclusive assignment: this rank's candidates stay on the device (59 GB for CelebA-128)
+    k = int(exclusive_k)
+    stream_k = NNK_STREAM and 2 <= k <= hip_ops.NNK_MAX_K
+    best_d2, best_idx = hip_ops.nnk_state(data_size, k, device) if stream_k else hip_ops.nn1_state(data_size, device)
+    fold = hip_ops.nnk_update_raw if stream_k else hip_ops.nn1_update_raw
+    # Exclusive assignment with more than NNK_MAX_K neighbours (or IGAN_NNK_STREAM=0): this rank's candidates stay on the device
+    # (59 GB for CelebA-128; at 256x256 they do not fit).  Up to NNK_MAX_K the k-NN lists are streamed and nothing is kept.
+    resident = [] if (k > 1 and not stream_k) else None
     # Candidates are generated `candidate_batch_size` at a time like the reference (:359-366) but searched in PACKS of several
     # batches: the distance GEMM of one 256-candidate batch against a 4096-query chunk is 64 tiles -- a quarter of the
     # device -- and ran at 31 TFLOP/s; a [query_chunk x dim] x [dim x pack] product fills it (profiles/r03_refresh_*.txt).
@@ -229,14 +273,14 @@ def imle_refresh(G, training_set_rec, latent_candidates, label_candidates, data_
                 continue
             cnorm = hip_ops.row_sqnorm_raw(cand)
             for q0 in range(0, data_size, query_chunk):
-                hip_ops.nn1_update_raw(reals[q0:q0 + query_chunk], rnorm[q0:q0 + query_chunk], cand, cnorm,
-                                       best_d2[q0:q0 + query_chunk], best_idx[q0:q0 + query_chunk], c0)
+                fold(reals[q0:q0 + query_chunk], rnorm[q0:q0 + query_chunk], cand, cnorm,
+                     best_d2[q0:q0 + query_chunk], best_idx[q0:q0 + query_chunk], c0)
+    if stream_k:
+        return unpack_best(best_d2, best_idx)       # an untouched slot is (INT32_MAX, +inf): "no candidate", as the resident path pads
     if resident is not None:
-        # k nearest candidates of every real over this rank's shard, merged over the ranks, then the reference's greedy
-        # exclusive pick on the host (identical on every rank: same inputs)
+        # k nearest candidates of every real over this rank's shard
         db = DCI(pdim, device=device)
         base = torch.cat([torch.arange(c0, c0 + c.shape[0], device=device) for c0, c in resident]) if resident else torch.zeros(0, dtype=torch.int64, device=device)
-        k = int(exclusive_k)
         if resident:
             db._data = torch.cat([c for _, c in resident], dim=0)
             db._norms = hip_ops.row_sqnorm_raw(db._data)
@@ -248,16 +292,8 @@ def imle_refresh(G, training_set_rec, latent_candidates, label_candidates, data_
             pad = k - gi.shape[1]
             gi = torch.cat([gi, torch.full((data_size, pad), 2 ** 31 - 1, dtype=torch.int64, device=device)], dim=1)
             ld = torch.cat([ld, torch.full((data_size, pad), float('inf'), dtype=torch.float64, device=device)], dim=1)
-        if world > 1:
-            all_i = [torch.empty_like(gi) for _ in range(world)]; all_d = [torch.empty_like(ld) for _ in range(world)]
-            torch.distributed.all_gather(all_i, gi); torch.distributed.all_gather(all_d, ld)
-            gi, ld = torch.cat(all_i, dim=1), torch.cat(all_d, dim=1)
-            o = torch.argsort(gi, dim=1, stable=True); gi, ld = torch.gather(gi, 1, o), torch.gather(ld, 1, o)
-            o = torch.argsort(ld, dim=1, stable=True); gi, ld = torch.gather(gi, 1, o)[:, :k], torch.gather(ld, 1, o)[:, :k]
-        return exclusive_assignment(gi.cpu().numpy(), ld.cpu().numpy())
-    combine_best_(best_d2, best_idx, world)
-    idx, dist = unpack_best(best_d2, best_idx)
-    return idx.cpu().numpy(), dist.cpu().numpy().astype(np.float64)
+        return gi, ld
+    return best_d2, best_idx
 
 #----------------------------------------------------------------------------
 # Main training script.

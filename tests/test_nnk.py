@@ -1,0 +1,105 @@
+"""CPU: the streaming exact k-NN with indices (igan_nnk_update, csrc/nnk.hip).  The entry point is declared, exported and bound
+without an ABI bump, validates its arguments before anything touches a device, and the Python layer has no CPU path."""
+import os
+import re
+
+import pytest
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+INT32_MAX = 2 ** 31 - 1
+
+
+def test_entry_point_is_declared_exported_and_bound():
+    from inclusivegan_amd import _abi
+    lib = _abi.get_plugin()
+    header = open(os.path.join(ROOT, 'include', 'igan_hip.h')).read()
+    code = re.sub(r'/\*.*?\*/', '', header, flags=re.S)
+    assert re.search(r'\bint igan_nnk_update\s*\(', code)
+    assert hasattr(lib, 'igan_nnk_update')
+    restype, argtypes = _abi.SIGNATURES['igan_nnk_update']
+    assert len(argtypes) == 13                                          # stream, 7 buffers, nq, nc, dim, k, idx_base
+    assert lib.igan_abi_version() == _abi.ABI_VERSION == 10             # a new export only: no bump
+    note = re.search(r'added under 10 without a bump.*?\*/', header, flags=re.S).group(0)
+    assert 'igan_nnk_update' in note
+    makefile = open(os.path.join(ROOT, 'inclusivegan_amd', 'csrc', 'Makefile')).read()
+    assert 'nnk.hip' in re.search(r'^SRCS = (.*)$', makefile, flags=re.M).group(1).split()
+
+
+def test_entry_point_validates_without_a_device():
+    from inclusivegan_amd import _abi
+    lib = _abi.get_plugin()
+    P = 1 << 20           # never dereferenced: validation fails first
+    bad, unsupported = _abi.IGAN_ERR_INVALID_ARGUMENT, _abi.IGAN_ERR_UNSUPPORTED
+    bufs = ('query', 'qnorm', 'cand', 'cnorm', 'best_d2', 'best_idx', 'dots')
+
+    def update(nq=40, nc=100, dim=64, k=10, idx_base=0, **null):
+        ptrs = [None if b in null else P for b in bufs]
+        return lib.igan_nnk_update(None, *ptrs, nq, nc, dim, k, idx_base)
+
+    for k in (0, 17, -1):
+        assert update(k=k) == unsupported, k
+        assert b'1 <= k <= 16' in lib.igan_last_error()
+    for b in bufs:
+        assert update(**{b: None}) == bad, b
+        assert b'null buffer' in lib.igan_last_error()
+    for size in ('nq', 'nc', 'dim'):
+        assert update(**{size: 0}) == bad, size
+        assert b'sizes must be positive' in lib.igan_last_error()
+    assert update(idx_base=-1) == bad and b'overflows int32' in lib.igan_last_error()
+    assert update(idx_base=INT32_MAX - 99) == bad and b'overflows int32' in lib.igan_last_error()      # idx_base + nc = INT32_MAX + 1
+    # the operand limits of igan_conv2d
+    assert update(nq=1 << 20, dim=1 << 10) == bad and b'2 GiB' in lib.igan_last_error()
+    assert update(nc=1 << 20, dim=1 << 10) == bad and b'2 GiB' in lib.igan_last_error()
+    assert update(nq=1 << 16, nc=1 << 16, dim=4) == bad and b'product block too large' in lib.igan_last_error()
+    with pytest.raises(NotImplementedError):
+        _abi.check(update(k=17))
+    with pytest.raises(ValueError):
+        _abi.check(update(nq=0))
+
+
+def test_state_shapes_dtypes_and_fill():
+    from inclusivegan_amd import hip_ops
+    assert hip_ops.NNK_MAX_K == 16
+    for k in (1, 3, 16):
+        d2, idx = hip_ops.nnk_state(5, k, 'cpu')
+        assert d2.shape == idx.shape == (5, k)
+        assert d2.dtype == torch.float64 and idx.dtype == torch.int32
+        assert d2.is_contiguous() and idx.is_contiguous()
+        assert bool(torch.isposinf(d2).all()) and bool((idx == INT32_MAX).all())
+    for k in (0, 17, -1):
+        with pytest.raises(ValueError):
+            hip_ops.nnk_state(5, k, 'cpu')
+
+
+def test_python_layer_has_no_cpu_path_and_checks_dtypes():
+    from inclusivegan_amd import hip_ops
+    q, c = torch.zeros(8, 4), torch.zeros(6, 4)
+    d2, idx = hip_ops.nnk_state(8, 2, 'cpu')
+    with pytest.raises(RuntimeError, match='no CPU path'):
+        hip_ops.nnk_update_raw(q, torch.zeros(8), c, torch.zeros(6), d2, idx, 0)
+    with pytest.raises((TypeError, RuntimeError)):
+        hip_ops.nnk_update_raw(q.double(), torch.zeros(8), c, torch.zeros(6), d2, idx, 0)
+
+
+def test_dci_routes_k_between_2_and_16_to_the_streaming_kernel(monkeypatch):
+    """DCI.query: k = 1 on query_device, 2 .. NNK_MAX_K on query_device_nnk, beyond that on query_device_k."""
+    from inclusivegan_amd.dci_code import dci as D
+    db = D.DCI(4, device='cpu')
+    db._data = torch.zeros(40, 4)
+    calls = []
+
+    def fake(name):
+        def fn(q, k=1, *a, **kw):
+            calls.append((name, k))
+            shape = (q.shape[0],) if name == 'nn1' else (q.shape[0], k)
+            return torch.zeros(shape, dtype=torch.int64), torch.zeros(shape, dtype=torch.float64)
+        return fn
+
+    monkeypatch.setattr(db, 'query_device', fake('nn1'))
+    monkeypatch.setattr(db, 'query_device_nnk', fake('nnk'))
+    monkeypatch.setattr(db, 'query_device_k', fake('k'))
+    for k in (1, 2, 10, 16, 17, 40):
+        idx, dist = db.query(torch.zeros(3, 4), num_neighbours=k)
+        assert len(idx) == 3 and idx[0].shape == (k,)
+    assert calls == [('nn1', 1), ('nnk', 2), ('nnk', 10), ('nnk', 16), ('k', 17), ('k', 40)]
