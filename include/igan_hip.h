@@ -484,7 +484,7 @@ int igan_mbstd_bwd(igan_stream_t stream, const float* x, const float* dy, float*
  * as a direct difference in fp64 (compute_dist, dci_code/src/util.c:62-69, before its sqrt), i.e. the
  * result equals an fp64 brute-force search (ties go to the lower index).  The fp32 MFMA product
  * |q|^2 + |c|^2 - 2 q.c only screens: candidates whose error interval (relative half-width
- * 2^-22 * sqrt(dim) of |q|^2 + |c|^2) cannot reach the best known upper bound are dropped, the rest are
+ * (dim + 2) * 2^-24, a rounding-error bound, of |q|^2 + |c|^2) cannot reach the best known upper bound are dropped, the rest are
  * measured exactly.  Initialise best_d2 to +infinity and best_idx to INT32_MAX; candidates can be streamed
  * batch after batch with increasing idx_base, the running minimum is order-independent, so the result is
  * deterministic.  A candidate with a non-finite product or distance never wins.
@@ -521,7 +521,7 @@ int igan_nnk_update(igan_stream_t stream, const float* query, const float* qnorm
  * Exact k-NN manifold search for the precision / recall metric (reference: metrics/precision_recall.py).
  * Both entries take the products of one candidate batch from the exact-fp32 MFMA like igan_nn1_update
  * (dots: caller workspace, nq*nc floats), screen with |q|^2 + |c|^2 - 2 q.c and its error interval (relative
- * half-width 2^-22 * sqrt(dim) of |q|^2 + |c|^2) and measure every pair the interval cannot decide as a
+ * half-width (dim + 2) * 2^-24, a rounding-error bound, of |q|^2 + |c|^2) and measure every pair the interval cannot decide as a
  * direct difference in fp64 -- the squared distance of igan_nn1_update, symmetric, 0 for identical rows.
  * A non-finite exact distance counts as +infinity and is never within a radius.  Candidate batches may be
  * streamed in any order; the results do not depend on it.  1 <= kcap <= 16, 1 <= nk <= 8; the operand
@@ -553,7 +553,7 @@ int igan_manifold_member_update(igan_stream_t stream, const float* query, const 
  * MiniBatchKMeans behind _cluster_into_bins): the nearest centre of every row and the per-centre sums of the rows.
  *   (d2[i], label[i]) = lexicographic min over centres j of (|X_i - C_j|^2, j)
  * with the squared distance of igan_nn1_update: the exact-fp32 MFMA product |x|^2 + |c|^2 - 2 x.c only screens (relative
- * half-width 2^-22 * sqrt(dim) of |x|^2 + |c|^2), every centre the interval cannot rule out is measured as a direct
+ * half-width (dim + 2) * 2^-24, a rounding-error bound, of |x|^2 + |c|^2), every centre the interval cannot rule out is measured as a direct
  * difference in fp64 -- labels and d2 equal an fp64 brute force on the same fp32 rows, ties go to the lower index.  A row
  * whose distances are all non-finite gets label -1 and d2 = +infinity and contributes to nothing below.
  *   sums[j] = sum of X_i over label[i] == j, count[j] = the number of such rows, inertia[0] = sum of d2[i] over labelled rows

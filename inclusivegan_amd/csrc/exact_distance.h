@@ -8,11 +8,31 @@
 
 namespace igan {
 
-// Relative half-width of the interval the fp32 cancellation form |q|^2 + |c|^2 - 2 q.c is trusted to: the dot product is an
-// fp32 FMA chain of `dim` terms (error ~ 0.3 * 2^-24 * sqrt(dim) * |q.c| statistically; measured 3.5e-7 * sum|a b| at dim 4096),
-// the norms are fp64 sums rounded to fp32.  2^-22 * sqrt(dim) (5.3e-5 at dim 49 152) leaves an order of magnitude of margin;
-// a wider interval only costs more exact evaluations, never a wrong answer.
-__device__ __forceinline__ double nn1_tol(int dim) { return fmax(2.384185791015625e-07 * sqrt((double)dim), 1e-6); }
+// Relative half-width of the interval the fp32 cancellation form a = |q|^2 + |c|^2 - 2 q.c is trusted to:
+//     |a - d2_exact(q, c)|  <=  nn1_tol(dim) * (|q|^2 + |c|^2)
+// as a BOUND, not an estimate: a pair the interval rules out is never measured, so a violation is a silently wrong neighbour.
+//   * the product.  The widest chain any product family runs is ONE accumulator over the whole reduction (distance_products()
+//     passes splits = 1): conv_fwd_kernel / conv_fwd_dma_kernel issue dim / 2 v_mfma_f32_32x32x2_f32 into one register, and the
+//     instruction adds its two products one after the other, each with a rounding -- L = dim accumulate steps (measured: the
+//     device's error on flat rows is that of a sequential fp32 sum with one product per step, not two).  dense_small_kernel and
+//     thin_out_kernel split the reduction among lanes and fold: shorter chains.  Every order of `dim` products in which a term
+//     meets at most `dim` roundings obeys |fl(q.c) - q.c| <= gamma_dim * sum|q_i c_i| <= gamma_dim * (|q|^2 + |c|^2) / 2 with
+//     gamma_n = n u / (1 - n u), u = 2^-24; a holds twice that error.
+//   * the norms are fp64 sums rounded to fp32: u * (|q|^2 + |c|^2) more, and the kernels' t is formed from the rounded norms,
+//     which can fall short of the true ones by (1 - u).
+// (dim + 2) u / (1 - (dim + 2) u) covers the three (2.9e-3 at dim 49 152).  The bound is attained to within a factor of a few
+// by rows whose products all have one sign and one size -- flat images: blank or saturated frames, a collapsed generator --
+// where every step rounds the same way and the error grows like dim: worst measured use of the interval 0.249 on flat rows on
+// every tile kernel (conv_fwd_dma_kernel and the 128x128, 128x64, 128x32 and 32x128 instantiations of conv_fwd_kernel, vector
+// and scalar loads) at every dim from 768 to 49 152, 0.025 on dense_small_kernel, 0.005 on thin_out_kernel; on rows that are
+// not flat at most 0.035 (all-positive, offset and noisy-flat rows) and 0.01 (zero-mean rows) -- profiles/screening_interval.txt,
+// asserted <= 0.5 per family by tests/test_gpu_screening.py.  The earlier statistical interval 2^-22 sqrt(dim)
+// (errors as a random walk) was exceeded 13.8 times over on flat rows at dim 49 152 and lost the true neighbour there.
+// A wider interval only costs more exact evaluations, never a wrong answer.
+__device__ __forceinline__ double nn1_tol(int dim) {
+    const double x = ((double)dim + 2.0) * 5.9604644775390625e-08;      // (dim + 2) * 2^-24
+    return (x < 0.5) ? x / (1.0 - x) : 1e300;      // past dim = 2^23 the bound says nothing: every pair is measured
+}
 
 // Squared distance of two rows as a direct difference with fp64 accumulation (compute_dist, dci_code/src/util.c:62-69,
 // before its sqrt), by one whole wavefront; the result is in every lane.  Fixed summation order: deterministic.

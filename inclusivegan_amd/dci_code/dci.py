@@ -199,9 +199,9 @@ class DCI(object):
 
         The short list is CHECKED before it is trusted: every candidate that was screened out has a screening distance of at
         least the worst kept one, hence an exact one of at least that minus the screening error tol * (|q|^2 + max |c|^2).  `tol`
-        is the 1-NN kernel's nn1_tol = 2^-22 sqrt(dim): a STATISTICAL bound on the rounding error of a dim-long fp32 dot product
-        (random-walk growth, ~4 standard deviations), not the worst case dim * 2^-24 -- the same assumption the 1-NN screening
-        makes.  Queries whose check fails are searched again with four times the margin (only those queries; the margin always
+        is the search kernels' nn1_tol (csrc/exact_distance.h): (dim + 2) u / (1 - (dim + 2) u), u = 2^-24, a BOUND on the rounding
+        error of a dim-long fp32 dot product in any summation order plus the norms' rounding -- flat rows come within a factor of
+        four of it, where a random-walk estimate (2^-22 sqrt(dim)) is exceeded many times over.  Queries whose check fails are searched again with four times the margin (only those queries; the margin always
         grows).  Past `max_keep` kept candidates -- near-tied candidates, e.g. a collapsed generator -- the list is no longer
         widened: the exact k-th distance already found bounds the true one from above, so only candidates whose screening
         distance lies within the slack of it can matter; they are selected by threshold and measured exactly in slabs, which
@@ -210,7 +210,8 @@ class DCI(object):
         n = self.num_points
         out_i = torch.empty((nq, k), device=self.device, dtype=torch.int64)
         out_d = torch.empty((nq, k), device=self.device, dtype=torch.float64)
-        tol = max(2.0 ** -22 * float(np.sqrt(self.dim)), 1e-6)
+        tol = (self.dim + 2.0) * 2.0 ** -24
+        tol = tol / (1.0 - tol) if tol < 0.5 else 1e300
         cmax = float(self._norms.max()) if n else 0.0
         self.last_margins = []
         self.last_threshold_queries = 0
