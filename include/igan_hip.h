@@ -399,7 +399,8 @@ int igan_dense_small_wgrad2_grouped(igan_stream_t stream, const igan_dense_wgrad
 
 /* out[m, j, :] = sum over the groups l with slot[l] == j, in order, of src[l, m, :]  (zero where no group names j): the per-layer
  * latent gradients [count, M, D] of one synthesis pass gathered into the gradient of the latents [M, L, D].  `slot` is a HOST
- * pointer (count <= IGAN_DENSE_MAX_GROUPS entries).  D % 4 == 0; deterministic. */
+ * pointer (count <= IGAN_DENSE_MAX_GROUPS entries), every entry in [0, L): a value outside is IGAN_ERR_INVALID_ARGUMENT, not a
+ * group left out.  D % 4 == 0; deterministic. */
 int igan_rows_group_sum(igan_stream_t stream, const float* src, const int* slot, int count, float* out, int M, int L, int D);
 
 /* out[i] = sum_t w[t*n + i]^2  (sum over the filter taps of the squared weights: the [Cin,Cout] matrix of the

@@ -537,6 +537,8 @@ extern "C" int igan_rows_group_sum(igan_stream_t stream_, const float* src, cons
     IGAN_REQUIRE(M >= 1 && L >= 1 && D >= 4 && D % 4 == 0 && (long long)M * L * D <= INT32_MAX, "rows_group_sum: D must be a positive multiple of 4");
     IGAN_REQUIRE(((((uintptr_t)src) | ((uintptr_t)out)) & 15) == 0, "rows_group_sum: buffers must be 16-byte aligned");
     RowsSumArgs A;
+    for (int i = 0; i < count; i++)      // a slot outside the latents would drop that layer's gradient without a word
+        IGAN_REQUIRE(slot[i] >= 0 && slot[i] < L, "rows_group_sum: slot[%d] = %d is outside [0, %d)", i, slot[i], L);
     for (int i = 0; i < IGAN_DENSE_MAX_GROUPS; i++) A.slot[i] = i < count ? slot[i] : -1;
     const int total = M * L * (D / 4);
     hipLaunchKernelGGL(rows_group_sum_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, (hipStream_t)stream_, src, out, A, count, M, L, D / 4);

@@ -35,7 +35,7 @@ inline int check_hip(hipError_t e, const char* what) {
         if (e__ != hipSuccess) return ::igan::check_hip(e__, what); \
     } while (0)
 
-// dense_small.hip: small-batch (M <= 32 rows) dense layers, dispatched from igan_conv2d / igan_conv2d_wgrad
+// dense_small.hip: small-batch (M <= IGAN_DENSE_MAX_ROWS = 64 rows) dense layers, dispatched from igan_conv2d / igan_conv2d_wgrad
 bool dense_small_ok(int M, int K, int N, const void* x, const void* w, bool wt);
 bool dense_small_fits(long long M, long long K, long long N, long long ldx);
 int dense_small_rows(int M);

@@ -1384,7 +1384,7 @@ def style_mod_fusable(y, a_w, w, demodulate):
 
 
 class StyleModFn(torch.autograd.Function):
-    """(s, d) of modulated_conv2d_layer (networks_stylegan2.py:99-107) for a batch of at most 32 latents:
+    """(s, d) of modulated_conv2d_layer (networks_stylegan2.py:99-107) for a batch of at most 64 latents (IGAN_DENSE_MAX_ROWS):
         s = c_a * y . A + b + 1                      [N, Cin]
         d = rsqrt(c_w^2 * (s^2 . wsq) + 1e-8)        [N, Cout],  wsq = sum_taps w^2 (passed in: cached per training op)
     two launches forward; backward five (style gradient + bias gradient, d wsq, its spread onto the filter taps,
