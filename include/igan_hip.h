@@ -506,8 +506,11 @@ int igan_nn1_update(igan_stream_t stream, const float* query, const float* qnorm
  * igan_nn1_update (a direct difference in fp64); the fp32 MFMA product screens with the same error interval and every
  * pair it cannot rule out is measured exactly.  Initialise best_d2 to +infinity and best_idx to INT32_MAX.  The state is a
  * function of the set of (row, index) pairs fed -- not of the order or the boundaries of the batches, bits of the distances
- * included -- and with k = 1 it is igan_nn1_update's, bit for bit.  A candidate whose exact distance is not finite never
- * enters; with fewer than k finite candidates the trailing slots stay (+infinity, INT32_MAX).
+ * included -- and with k = 1 it is igan_nn1_update's, bit for bit, as long as no screening value is NaN.  The two differ for
+ * a candidate whose fp32 product or norms overflow (rows of magnitude ~1e19 and beyond), so that |q|^2 + |c|^2 - 2 q.c is
+ * NaN, and whose exact distance is finite: igan_nn1_update never measures such a candidate and it never wins; igan_nnk_update
+ * (like the manifold entries and igan_kmeans_step) measures it and it enters on its fp64 distance.  A candidate whose exact
+ * distance is not finite never enters; with fewer than k finite candidates the trailing slots stay (+infinity, INT32_MAX).
  * 1 <= k <= 16 (IGAN_ERR_UNSUPPORTED beyond); non-null buffers, positive sizes, idx_base >= 0 and idx_base + nc <=
  * INT32_MAX, the operand limits of igan_conv2d (IGAN_ERR_INVALID_ARGUMENT).  Arguments are validated before anything
  * touches a device.

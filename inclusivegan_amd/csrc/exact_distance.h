@@ -1,7 +1,8 @@
-// The ONE definition of the exact distance that nn1.hip (IMLE 1-NN) and knn_manifold.hip (pr50k3) share.
+// The ONE definition of the exact distance that the searches of exact_search.hip (IMLE 1-NN and k-NN, pr50k3) and kmeans.hip share.
 // The radii the manifold search produces, the distances it compares with them and the 1-NN distances are the SAME function of
-// two rows (symmetric, d2(a, a) == 0, summation order fixed by dim and the 16-byte alignment of the rows alone) because both
-// files compile these definitions; the screening product and its error interval are shared for the same reason.
+// two rows (symmetric, d2(a, a) == 0, summation order fixed by dim and the 16-byte alignment of the rows alone) because every
+// kernel compiles these definitions; the screening product and its error interval are shared for the same reason, and the
+// procedure built on them is exact_search.h.
 #pragma once
 #include "igan_common.h"
 #include <cmath>
@@ -31,7 +32,7 @@ namespace igan {
 // A wider interval only costs more exact evaluations, never a wrong answer.
 __device__ __forceinline__ double nn1_tol(int dim) {
     const double x = ((double)dim + 2.0) * 5.9604644775390625e-08;      // (dim + 2) * 2^-24
-    return (x < 0.5) ? x / (1.0 - x) : 1e300;      // past dim = 2^23 the bound says nothing: every pair is measured
+    return (x <= 0.5) ? x / (1.0 - x) : 1e300;     // 1 at dim = 2^23 - 2, still a bound; past it, it says nothing: every pair is measured
 }
 
 // Squared distance of two rows as a direct difference with fp64 accumulation (compute_dist, dci_code/src/util.c:62-69,

@@ -4,7 +4,7 @@
 // (precision-recall-distributions/prd_score.py:125-127); every step of that algorithm is "nearest centre of each row, then
 // the per-centre sums of the rows".  The nearest centre is the lexicographic minimum of (d2(x, c_j), j) with the ONE exact
 // distance of exact_distance.h -- what an fp64 brute force on the same fp32 rows returns, ties to the lower index.
-// MI355X design: the 1-NN pattern (nn1.hip) with the centres as the candidate batch, k <= 64 so that a lane owns a centre.
+// MI355X design: the 1-NN pattern (exact_search.hip) with the centres as the candidate batch, k <= 64 so that a lane owns a centre.
 //   products   [n x dim] x [dim x k] on the exact-fp32 MFMA through distance_products(): |x|^2 + |c|^2 - 2 x.c only SCREENS
 //   assign     one wavefront per row: smallest upper bound, then every centre whose interval reaches below it is measured
 //              as a direct difference in fp64 (wave_sqdist)
@@ -14,14 +14,13 @@
 // Slices, strides and trees are functions of (n, k, dim) alone and there is no floating-point atomic: two calls give the
 // same bits.
 #include "igan_common.h"
-#include "exact_distance.h"
+#include "exact_search.h"
 
 #include <cmath>
 
 namespace {
 
-using igan::nn1_tol;         // exact_distance.h: the one definition, shared with nn1.hip and knn_manifold.hip
-using igan::wave_sqdist;
+using namespace igan;        // exact_search.h: the screening procedure, shared with exact_search.hip
 
 constexpr int KM_MAX_K = 64;
 constexpr int KM_MAX_DIM = 4096;
@@ -54,29 +53,16 @@ __global__ __launch_bounds__(256) void kmeans_assign_kernel(const float* __restr
     const int lane = threadIdx.x & 63;
     if (row >= n) return;
     const double inf = (double)INFINITY;
-    const double tol = nn1_tol(dim);
-    double lo = 0.0, hi = inf;
-    if (lane < k) {
-        const double qn = (double)xnorm[row], cn = (double)cnorm[lane];
-        const double a = qn + cn - 2.0 * (double)dots[(size_t)row * k + lane];
-        const double t = tol * (qn + cn);
-        lo = a - t;
-        hi = a + t;
-    }
-    double u = (hi < inf) ? hi : inf;       // a NaN bound counts as +inf
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const double o = __shfl_xor(u, off, 64);
-        u = (o < u) ? o : u;
-    }
-    unsigned long long mask = __ballot(lane < k && !(lo > u));
+    const Screen s{dots + (size_t)row * k, cnorm, (double)xnorm[row], nn1_tol(dim)};
+    Interval iv{0.0, inf};
+    if (lane < k) iv = s(lane);
+    double u = wave_min((iv.hi < inf) ? iv.hi : inf);       // a NaN bound counts as +inf
     const float* xrow = X + (size_t)row * dim;
     double bd = inf;
     int bi = -1;
-    while (mask) {
-        const int j = __ffsll((long long)mask) - 1;
-        mask &= mask - 1;
-        if (__shfl(lo, j, 64) > u) continue;                     // u has come down since the ballot
+    int j;
+    for (ContenderStrip strip(lane < k && contends_unless_ruled_out(iv.lo, u)); strip.next(j);) {
+        if (!contends_unless_ruled_out(__shfl(iv.lo, j, 64), u)) continue;      // u has come down since the ballot
         const double e = wave_sqdist(xrow, C + (size_t)j * dim, dim, lane);
         if (e < bd) { bd = e; bi = j; }                          // ascending j: a tie keeps the lower index; false for NaN / +inf
         u = (e < u) ? e : u;

@@ -15,7 +15,7 @@ never visit the host (the reference materialises a 118 GB fp64 array, training_l
 
 `num_neighbours == 1` (the default, non-exclusive IMLE assignment, training_loop.py:398) runs entirely in the streaming
 HIP kernel, and so does `2 <= num_neighbours <= hip_ops.NNK_MAX_K` (the exclusive variant, :382-396): the same search keeping
-the k smallest (distance, index) pairs per query (`query_device_nnk`, csrc/nnk.hip).  Beyond NNK_MAX_K neighbours
+the k smallest (distance, index) pairs per query (`query_device_nnk`, csrc/exact_search.hip).  Beyond NNK_MAX_K neighbours
 `query_device_k` screens with the same MFMA products and re-ranks a short list exactly with torch ops.
 """
 import numpy as np
@@ -122,33 +122,26 @@ class DCI(object):
         dist = dist.cpu().numpy().astype(np.float64)
         return [idx[i] for i in range(idx.shape[0])], [dist[i] for i in range(dist.shape[0])]
 
-    def query_device(self, q):
-        """q: device fp32 [nq, dim] -> (int64 idx [nq], fp64 Euclidean dist [nq]) on the device."""
-        nq = int(q.shape[0])
-        best_d2, best_idx = hip_ops.nn1_state(nq, self.device)
-        n = self.num_points
-        for q0 in range(0, nq, self.query_chunk):
+    def _stream_search(self, q, state, update):
+        """Fold every candidate into `state` = (best_d2, best_idx), a query chunk against a candidate chunk per `update` call."""
+        best_d2, best_idx = state
+        for q0 in range(0, int(q.shape[0]), self.query_chunk):
             qs = q[q0:q0 + self.query_chunk]
             qn = hip_ops.row_sqnorm_raw(qs)
-            for c0 in range(0, n, self.cand_chunk):
-                hip_ops.nn1_update_raw(qs, qn, self._data[c0:c0 + self.cand_chunk], self._norms[c0:c0 + self.cand_chunk],
-                                       best_d2[q0:q0 + self.query_chunk], best_idx[q0:q0 + self.query_chunk], c0)
+            for c0 in range(0, self.num_points, self.cand_chunk):
+                update(qs, qn, self._data[c0:c0 + self.cand_chunk], self._norms[c0:c0 + self.cand_chunk],
+                       best_d2[q0:q0 + self.query_chunk], best_idx[q0:q0 + self.query_chunk], c0)
         return unpack_best(best_d2, best_idx)
+
+    def query_device(self, q):
+        """q: device fp32 [nq, dim] -> (int64 idx [nq], fp64 Euclidean dist [nq]) on the device."""
+        return self._stream_search(q, hip_ops.nn1_state(int(q.shape[0]), self.device), hip_ops.nn1_update_raw)
 
     def query_device_nnk(self, q, k):
         """q: device fp32 [nq, dim], 1 <= k <= hip_ops.NNK_MAX_K -> (int64 idx [nq, k], fp64 Euclidean dist [nq, k]) on the device,
         ascending, ties to the lower index: the streaming search of `query_device` keeping k (distance, index) pairs per query.
         With fewer than k candidates at a finite distance the trailing slots are (INT32_MAX, +inf)."""
-        nq = int(q.shape[0])
-        best_d2, best_idx = hip_ops.nnk_state(nq, k, self.device)
-        n = self.num_points
-        for q0 in range(0, nq, self.query_chunk):
-            qs = q[q0:q0 + self.query_chunk]
-            qn = hip_ops.row_sqnorm_raw(qs)
-            for c0 in range(0, n, self.cand_chunk):
-                hip_ops.nnk_update_raw(qs, qn, self._data[c0:c0 + self.cand_chunk], self._norms[c0:c0 + self.cand_chunk],
-                                       best_d2[q0:q0 + self.query_chunk], best_idx[q0:q0 + self.query_chunk], c0)
-        return unpack_best(best_d2, best_idx)
+        return self._stream_search(q, hip_ops.nnk_state(int(q.shape[0]), k, self.device), hip_ops.nnk_update_raw)
 
     def _screen(self, qs, qn, keep):
         """Top-`keep` candidates per query by the fp32 MFMA screening distance over all candidate batches -> (d2 [nq, keep] ascending, idx)."""
@@ -210,8 +203,7 @@ class DCI(object):
         n = self.num_points
         out_i = torch.empty((nq, k), device=self.device, dtype=torch.int64)
         out_d = torch.empty((nq, k), device=self.device, dtype=torch.float64)
-        tol = (self.dim + 2.0) * 2.0 ** -24
-        tol = tol / (1.0 - tol) if tol < 0.5 else 1e300
+        tol = hip_ops.screening_tol(self.dim)
         cmax = float(self._norms.max()) if n else 0.0
         self.last_margins = []
         self.last_threshold_queries = 0

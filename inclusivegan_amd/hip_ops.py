@@ -2157,6 +2157,33 @@ def row_sqnorm_raw(a):
     return out
 
 
+def screening_tol(dim):
+    """nn1_tol of csrc/exact_distance.h, the relative half-width of the interval every exact search screens with:
+    (dim + 2) u / (1 - (dim + 2) u), u = 2^-24, up to 1 at dim = 2^23 - 2; past that the bound says nothing (1e300: every pair is
+    measured)."""
+    x = (dim + 2.0) * 2.0 ** -24
+    return x / (1.0 - x) if x <= 0.5 else 1e300
+
+
+def _search_operands(name, query, qnorm, cand, cnorm):
+    """The operands of every exact-search update: fp32 device tensors, made contiguous, query [nq, dim], cand [nc, dim] and their
+    norms in agreement -> (query, qnorm, cand, cnorm, dots [nq, nc] workspace)."""
+    _require_cuda_f32(query, qnorm, cand, cnorm)
+    query, qnorm, cand, cnorm = query.contiguous(), qnorm.contiguous(), cand.contiguous(), cnorm.contiguous()
+    nq, dim = query.shape
+    if cand.dim() != 2 or cand.shape[1] != dim or qnorm.numel() != nq or cnorm.numel() != cand.shape[0]:
+        raise ValueError('%s: shapes of query, cand and their norms do not agree' % name)
+    return query, qnorm, cand, cnorm, torch.empty((nq, cand.shape[0]), device=query.device, dtype=torch.float32)
+
+
+def _search_state(name, what, t, dtype, nq, ndim=2):
+    """A running state is written in place: contiguous `dtype` with one row per query."""
+    if t.dtype != dtype or not t.is_contiguous() or t.dim() != ndim:
+        raise TypeError('%s: %s must be contiguous %s with %d dimension(s)' % (name, what, str(dtype).replace('torch.', ''), ndim))
+    if t.shape[0] != nq:
+        raise ValueError('%s: %s must have one row per query' % (name, what))
+
+
 def nn1_state(nq, device):
     """Running minimum of igan_nn1_update for nq queries: (squared distance fp64 = +inf, candidate index int32 = INT32_MAX)."""
     return (torch.full((nq,), float('inf'), device=device, dtype=torch.float64),
@@ -2166,14 +2193,10 @@ def nn1_state(nq, device):
 def nn1_update_raw(query, qnorm, cand, cnorm, best_d2, best_idx, idx_base):
     """Fold one candidate batch into the running exact minimum (best_d2 fp64 [nq], best_idx int32 [nq]; contiguous views)."""
     lib = _abi.get_plugin()
-    _require_cuda_f32(query, qnorm, cand, cnorm)
-    if best_d2.dtype != torch.float64 or best_idx.dtype != torch.int32 or not (best_d2.is_contiguous() and best_idx.is_contiguous()):
-        raise TypeError('nn1_update: best_d2 must be contiguous float64 and best_idx contiguous int32')
-    query = query.contiguous()
-    cand = cand.contiguous()
-    nq, dim = query.shape
-    nc = cand.shape[0]
-    dots = torch.empty((nq, nc), device=query.device, dtype=torch.float32)
+    query, qnorm, cand, cnorm, dots = _search_operands('nn1_update', query, qnorm, cand, cnorm)
+    (nq, dim), nc = query.shape, cand.shape[0]
+    _search_state('nn1_update', 'best_d2', best_d2, torch.float64, nq, 1)
+    _search_state('nn1_update', 'best_idx', best_idx, torch.int32, nq, 1)
     _abi.check(lib.igan_nn1_update(_stream(), _ptr(query), _ptr(qnorm), _ptr(cand), _ptr(cnorm), _ptr(best_d2), _ptr(best_idx), _ptr(dots),
                                    nq, nc, dim, idx_base))
 
@@ -2194,19 +2217,13 @@ def nnk_update_raw(query, qnorm, cand, cnorm, best_d2, best_idx, idx_base):
     """Fold one candidate batch into the running k smallest exact (squared distance, index) pairs (best_d2 fp64 [nq, k],
     best_idx int32 [nq, k], ascending, ties to the lower index; contiguous views)."""
     lib = _abi.get_plugin()
-    _require_cuda_f32(query, qnorm, cand, cnorm)
-    if best_d2.dtype != torch.float64 or not best_d2.is_contiguous() or best_d2.dim() != 2:
-        raise TypeError('nnk_update: best_d2 must be contiguous float64 [nq, k]')
-    if best_idx.dtype != torch.int32 or not best_idx.is_contiguous() or best_idx.dim() != 2:
-        raise TypeError('nnk_update: best_idx must be contiguous int32 [nq, k]')
-    query = query.contiguous()
-    cand = cand.contiguous()
-    nq, dim = query.shape
-    nc = cand.shape[0]
-    if best_d2.shape[0] != nq or best_idx.shape != best_d2.shape or cand.shape[1] != dim or qnorm.numel() != nq or cnorm.numel() != nc:
-        raise ValueError('nnk_update: shapes of query, cand, norms, best_d2 and best_idx do not agree')
-    dots = torch.empty((nq, nc), device=query.device, dtype=torch.float32)
-    _abi.check(lib.igan_nnk_update(_stream(), _ptr(query), _ptr(qnorm.contiguous()), _ptr(cand), _ptr(cnorm.contiguous()), _ptr(best_d2), _ptr(best_idx),
+    query, qnorm, cand, cnorm, dots = _search_operands('nnk_update', query, qnorm, cand, cnorm)
+    (nq, dim), nc = query.shape, cand.shape[0]
+    _search_state('nnk_update', 'best_d2', best_d2, torch.float64, nq)
+    _search_state('nnk_update', 'best_idx', best_idx, torch.int32, nq)
+    if best_idx.shape != best_d2.shape:
+        raise ValueError('nnk_update: shapes of best_d2 and best_idx do not agree')
+    _abi.check(lib.igan_nnk_update(_stream(), _ptr(query), _ptr(qnorm), _ptr(cand), _ptr(cnorm), _ptr(best_d2), _ptr(best_idx),
                                    _ptr(dots), nq, nc, dim, best_d2.shape[1], idx_base))
 
 
@@ -2220,17 +2237,10 @@ def knn_radius_state(nq, kcap, device):
 def knn_radius_update_raw(query, qnorm, cand, cnorm, kth_d2):
     """Fold one candidate batch into the running kcap smallest exact squared distances (kth_d2 fp64 [nq, kcap] ascending; contiguous view)."""
     lib = _abi.get_plugin()
-    _require_cuda_f32(query, qnorm, cand, cnorm)
-    if kth_d2.dtype != torch.float64 or not kth_d2.is_contiguous() or kth_d2.dim() != 2:
-        raise TypeError('knn_radius_update: kth_d2 must be contiguous float64 [nq, kcap]')
-    query = query.contiguous()
-    cand = cand.contiguous()
-    nq, dim = query.shape
-    nc = cand.shape[0]
-    if kth_d2.shape[0] != nq or cand.shape[1] != dim or qnorm.numel() != nq or cnorm.numel() != nc:
-        raise ValueError('knn_radius_update: shapes of query, cand, norms and kth_d2 do not agree')
-    dots = torch.empty((nq, nc), device=query.device, dtype=torch.float32)
-    _abi.check(lib.igan_knn_radius_update(_stream(), _ptr(query), _ptr(qnorm.contiguous()), _ptr(cand), _ptr(cnorm.contiguous()), _ptr(kth_d2), _ptr(dots),
+    query, qnorm, cand, cnorm, dots = _search_operands('knn_radius_update', query, qnorm, cand, cnorm)
+    (nq, dim), nc = query.shape, cand.shape[0]
+    _search_state('knn_radius_update', 'kth_d2', kth_d2, torch.float64, nq)
+    _abi.check(lib.igan_knn_radius_update(_stream(), _ptr(query), _ptr(qnorm), _ptr(cand), _ptr(cnorm), _ptr(kth_d2), _ptr(dots),
                                           nq, nc, dim, kth_d2.shape[1]))
 
 
@@ -2238,21 +2248,15 @@ def manifold_member_update_raw(query, qnorm, cand, cnorm, cand_radius, member):
     """Mark member[q, s] = 1 (int32 [nq, nk], contiguous view, starts at 0) when a candidate of the batch has an exact squared
     distance <= cand_radius[c, s] (fp64 [nc, nk])."""
     lib = _abi.get_plugin()
-    _require_cuda_f32(query, qnorm, cand, cnorm)
+    query, qnorm, cand, cnorm, dots = _search_operands('manifold_member_update', query, qnorm, cand, cnorm)
+    (nq, dim), nc = query.shape, cand.shape[0]
     if cand_radius.dtype != torch.float64 or cand_radius.dim() != 2 or not cand_radius.is_cuda:
         raise TypeError('manifold_member_update: cand_radius must be a device float64 [nc, nk]')
-    if member.dtype != torch.int32 or not member.is_contiguous() or member.dim() != 2:
-        raise TypeError('manifold_member_update: member must be contiguous int32 [nq, nk]')
-    query = query.contiguous()
-    cand = cand.contiguous()
-    cand_radius = cand_radius.contiguous()
-    nq, dim = query.shape
-    nc = cand.shape[0]
-    nk = member.shape[1]
-    if member.shape[0] != nq or tuple(cand_radius.shape) != (nc, nk) or cand.shape[1] != dim or qnorm.numel() != nq or cnorm.numel() != nc:
-        raise ValueError('manifold_member_update: shapes of query, cand, norms, cand_radius and member do not agree')
-    dots = torch.empty((nq, nc), device=query.device, dtype=torch.float32)
-    _abi.check(lib.igan_manifold_member_update(_stream(), _ptr(query), _ptr(qnorm.contiguous()), _ptr(cand), _ptr(cnorm.contiguous()), _ptr(cand_radius),
+    _search_state('manifold_member_update', 'member', member, torch.int32, nq)
+    cand_radius, nk = cand_radius.contiguous(), member.shape[1]
+    if tuple(cand_radius.shape) != (nc, nk):
+        raise ValueError('manifold_member_update: shapes of cand, cand_radius and member do not agree')
+    _abi.check(lib.igan_manifold_member_update(_stream(), _ptr(query), _ptr(qnorm), _ptr(cand), _ptr(cnorm), _ptr(cand_radius),
                                                _ptr(member), _ptr(dots), nq, nc, dim, nk))
 
 

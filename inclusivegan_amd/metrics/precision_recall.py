@@ -8,7 +8,7 @@ Recall Metric for Assessing Generative Models").
     realism = radius(nearest, nhood_sizes[0]) / min d2, squared over squared                                     (:124-125)
 
 The reference fills [10 000 x n] float16 distance blocks on the GPUs and partitions them on the host.  Here the search is
-the exact streaming one of the 1-NN (csrc/knn_manifold.hip, csrc/nn1.hip): the fp32 MFMA product only screens, every pair it
+the exact streaming one of the 1-NN (csrc/exact_search.hip): the fp32 MFMA product only screens, every pair it
 cannot decide is measured as a direct difference in fp64, so radii, predictions and nearest indices equal an fp64 brute
 force on the same fp32 features; nothing larger than one product block exists and nothing but the results visits the host.
 `.D` therefore holds float64 SQUARED radii (the reference: float16).

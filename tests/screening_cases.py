@@ -1,8 +1,8 @@
 """Row families that are adversarial for the screening interval of the exact searches (csrc/exact_distance.h), their fp64
 brute force and the interval arithmetic restated, shared by tests/test_screening_cases.py (host) and
-tests/test_gpu_screening.py.  NumPy only: no device is needed to import it.
+tests/test_gpu_screening.py.  No device is needed to import it.
 
-Every exact search (nn1.hip, nnk.hip, knn_manifold.hip, kmeans.hip) forms a = |q|^2 + |c|^2 - 2 q.c from an fp32 product and
+Every exact search (exact_search.hip, kmeans.hip) forms a = |q|^2 + |c|^2 - 2 q.c from an fp32 product and
 measures a pair in fp64 only when [a - t, a + t], t = nn1_tol(dim) * (|q|^2 + |c|^2), cannot decide it.  That is sound only
 while |a - d2_exact| <= t; interval_use() is the ratio rho of the two, per pair.  On rows whose products all have one sign and
 one size (flat images) the rounding errors of a running fp32 sum do not cancel: they grow like dim, not like sqrt(dim).
@@ -24,9 +24,10 @@ U32 = 2.0 ** -24        # unit roundoff of fp32
 
 
 def nn1_tol(dim):
-    """csrc/exact_distance.h, `nn1_tol`: (dim + 2) u / (1 - (dim + 2) u), u = 2^-24 -- a bound for any order of `dim` roundings."""
-    x = (dim + 2.0) * U32
-    return x / (1.0 - x) if x < 0.5 else 1e300
+    """csrc/exact_distance.h, `nn1_tol`: (dim + 2) u / (1 - (dim + 2) u), u = 2^-24 -- a bound for any order of `dim` roundings.
+    Stated once in Python, by hip_ops.screening_tol (tests/test_exact_search.py holds it to the closed form)."""
+    from inclusivegan_amd import hip_ops
+    return hip_ops.screening_tol(dim)
 
 
 def statistical_tol(dim):
@@ -198,7 +199,7 @@ def row_sqnorm32(a):
 
 def interval_use(q, c, dots, qnorm, cnorm, d2=None, tol=nn1_tol):
     """rho[i, j] = |a - d2_exact| / t with a = qn + cn - 2 dot and t = nn1_tol(dim) * (qn + cn), in fp64 on the fp32 values the
-    kernels read, exactly as the fold kernels form them (nn1.hip pass 1).  rho <= 1 is what the screen needs."""
+    kernels read, exactly as the fold kernels form them (exact_search.h, screen_interval).  rho <= 1 is what the screen needs."""
     if d2 is None:
         d2 = exact_sqdist(q, c)
     qn = np.asarray(qnorm, np.float32).astype(np.float64)[:, None]
@@ -227,7 +228,7 @@ def chain_dots(q, c, n):
 
 
 def modelled_screen_keeps(q, c, dots, qnorm, cnorm, tol=nn1_tol):
-    """The 1-NN screen of nn1.hip on given products: the smallest upper bound a + t, then every candidate whose lower bound
+    """The 1-NN screen of exact_search.hip on given products: the smallest upper bound a + t, then every candidate whose lower bound
     a - t exceeds it is dropped.  -> bool [nq, nc], True where a candidate is still measured."""
     qn = np.asarray(qnorm, np.float32).astype(np.float64)[:, None]
     cn = np.asarray(cnorm, np.float32).astype(np.float64)[None, :]

@@ -1,4 +1,4 @@
-"""GPU: the streaming exact k-NN with indices (igan_nnk_update, csrc/nnk.hip) against the fp64 brute force of tests/imle_cases.py,
+"""GPU: the streaming exact k-NN with indices (igan_nnk_update, csrc/exact_search.hip) against the fp64 brute force of tests/imle_cases.py,
 through hip_ops, DCI.query and the exclusive branch of imle_refresh.  Indices must be equal; distances are held to the bar of
 tests/test_gpu_ops.py::test_knn_k_neighbours_vs_oracle, <= 1e-12 * max: the rows are fp32 and both sides sum direct differences
 in fp64, so they differ by the summation order alone (~sqrt(dim) * 2^-53 relative).

@@ -1,4 +1,4 @@
-"""GPU: k-NN precision / recall on the exact HIP manifold search (csrc/knn_manifold.hip) against the values the reference's
+"""GPU: k-NN precision / recall on the exact HIP manifold search (csrc/exact_search.hip) against the values the reference's
 own ManifoldEstimator produced (tests/golden/pr_golden.npz) and against an fp64 brute force on the same fp32 features.
 Predictions and nearest indices are EQUAL on every row, not close; radii agree to the accuracy of an fp64 sum."""
 import numpy as np

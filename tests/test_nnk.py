@@ -1,4 +1,4 @@
-"""CPU: the streaming exact k-NN with indices (igan_nnk_update, csrc/nnk.hip).  The entry point is declared, exported and bound
+"""CPU: the streaming exact k-NN with indices (igan_nnk_update, csrc/exact_search.hip).  The entry point is declared, exported and bound
 without an ABI bump, validates its arguments before anything touches a device, and the Python layer has no CPU path."""
 import os
 import re
@@ -23,7 +23,7 @@ def test_entry_point_is_declared_exported_and_bound():
     note = re.search(r'added under 10 without a bump.*?\*/', header, flags=re.S).group(0)
     assert 'igan_nnk_update' in note
     makefile = open(os.path.join(ROOT, 'inclusivegan_amd', 'csrc', 'Makefile')).read()
-    assert 'nnk.hip' in re.search(r'^SRCS = (.*)$', makefile, flags=re.M).group(1).split()
+    assert 'exact_search.hip' in re.search(r'^SRCS = (.*)$', makefile, flags=re.M).group(1).split()
 
 
 def test_entry_point_validates_without_a_device():

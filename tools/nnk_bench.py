@@ -83,8 +83,7 @@ def streamed(reals, rnorm, a, dev, fold, state, seed, sample=0):
     """Phase A: packs made, folded and discarded -> (seconds of the folds, bracket counts)."""
     buf = torch.empty((min(a.pack, a.nc), a.dim), device=dev, dtype=torch.float32)
     total, hi, lo = 0.0, 0, 0
-    tol = (a.dim + 2.0) * 2.0 ** -24
-    tol = tol / (1.0 - tol)          # nn1_tol, csrc/exact_distance.h
+    tol = hip_ops.screening_tol(a.dim)          # nn1_tol, csrc/exact_distance.h
     k = state[0].shape[1] if state[0].dim() == 2 else 1
     for pk, c0 in enumerate(range(0, a.nc, a.pack)):
         cand = fill_pack(buf[:min(a.pack, a.nc - c0)], pk, seed)
