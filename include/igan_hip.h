@@ -43,7 +43,8 @@ extern "C" {
  * igan_linear_svc_workspace_bytes, igan_linear_svc_grad, igan_linear_svc_hv, igan_linear_svc_linesearch, igan_linear_svc_predict,
  * igan_images_to_uint8, igan_images_from_uint8, igan_dense_small2_grouped, igan_dense_small_wgrad2_grouped, igan_rows_group_sum,
  * igan_scale_add, igan_kmeans_workspace_bytes, igan_kmeans_step, igan_moments_workspace_bytes, igan_moments_update, igan_moments_finalize,
- * igan_moments_merge, igan_class_hist_update, igan_prob_stats_update, igan_nnk_update). */
+ * igan_moments_merge, igan_class_hist_update, igan_prob_stats_update, igan_nnk_update, igan_softmax_xent_fwd, igan_softmax_xent_bwd,
+ * igan_xent_stats_update). */
 #define IGAN_ABI_VERSION 10
 
 typedef void* igan_stream_t; /* hipStream_t */
@@ -642,6 +643,41 @@ int igan_class_hist_update(igan_stream_t stream, const float* logits /* [n][K] *
                            int* labels /* [n] or NULL */, int n, int K);
 int igan_prob_stats_update(igan_stream_t stream, const float* probs /* [n][K] */, double* psum /* [K], accumulated */,
                            double* plogp /* [1], accumulated */, int n, int K);
+
+/* ------------------------------------------------------------------------
+ * Softmax cross-entropy against integer labels: the loss of the Stacked-MNIST mode classifier this project trains for itself
+ * (the reference ships no trainer for metrics/stacked_mnist_classifier.pkl, metrics/mode_counts.py:29).  Added without a
+ * version bump: three more exports, no struct or signature changes.  Arguments are validated before anything touches a
+ * device: a null pointer (pred of the forward alone may be NULL), n < 1, K < 1, n * K * 4 at or above 2 GiB, lse / loss_sum /
+ * counts not 8-byte aligned or another buffer not 4-byte aligned return IGAN_ERR_INVALID_ARGUMENT.  Inputs are dense
+ * row-major and need 4-byte alignment ONLY: a row of an odd K starts anywhere.  No workspace, no floating-point atomic: the
+ * bits are a function of (n, K), the data and the sequence of calls.
+ *
+ * igan_softmax_xent_fwd / _bwd replace torch.nn.functional.cross_entropy(logits, labels, reduction='none') and its
+ * gradient, as fp64 states them:
+ *     lse[i]  = m + log sum_k exp((double)x[i][k] - m),  m = max_k x[i][k]        evaluated and STORED in fp64
+ *     loss[i] = (float)(lse[i] - x[i][label[i]])
+ *     dlogits[i][k] = (float)(dloss[i] * (exp((double)x[i][k] - lse[i]) - (k == label[i])))     one rounding, from the stored lse
+ * (lse is evaluated as m + log1p(sum over k != argmax of exp(x[i][k] - m)) -- the arg-max column's term is exactly 1, and the
+ * logarithm of a sum rounded next to 1 would lose the digits of a confident row's lse -- and exp(a) - 1 at the label's column
+ * as expm1(a): a confident row has p within a few ulp of 1 there.)
+ * A row whose label lies outside [0, K) is ignored (the trainer pads with -1): loss 0, gradient row 0, nothing is read at the
+ * label's column; its lse and pred are still written.  pred[i] is np.argmax(x[i]) under exactly the rules of
+ * igan_class_hist_update (lowest index among equal maxima, the first NaN, 0 for a row of -infinity).  Non-finite values stay
+ * in their own row: a NaN or +infinity logit, or a row of -infinity, makes that row's lse, loss and gradient row NaN and
+ * changes no other row; a -infinity among finite logits contributes exactly 0.  Forward: one wavefront per row, lane sums in
+ * ascending column order, then a fixed tree over the lanes.  Backward: one thread per element.
+ *
+ * igan_xent_stats_update ACCUMULATES the numbers a trainer tick reports, over the rows whose label lies in [0, K):
+ *     loss_sum[0] += sum_i (double)loss[i]  in row order, by one owner        counts[0] += rows counted        counts[1] += rows with pred[i] == label[i]
+ * so the mean loss and accuracy of a tick are one device -> host copy.  A NaN loss makes loss_sum NaN, as the sum does. */
+int igan_softmax_xent_fwd(igan_stream_t stream, const float* logits /* [n][K] */, const int* labels /* [n] */, float* loss /* [n] */,
+                          double* lse /* [n] */, int* pred /* [n] or NULL */, int n, int K);
+int igan_softmax_xent_bwd(igan_stream_t stream, const float* logits /* [n][K] */, const int* labels /* [n] */, const double* lse /* [n] */,
+                          const float* dloss /* [n] */, float* dlogits /* [n][K] */, int n, int K);
+int igan_xent_stats_update(igan_stream_t stream, const float* loss /* [n] */, const int* labels /* [n] */, const int* pred /* [n] */,
+                           double* loss_sum /* [1], accumulated */, long long* counts /* [2]: rows counted, rows correct; accumulated */,
+                           int n, int K);
 
 /* ------------------------------------------------------------------------
  * Perceptual path length (reference: metrics/perceptual_path_length.py; ppl_zfull .. ppl2_wend).  Added without a

@@ -25,61 +25,14 @@
 //              One compute unit evaluates every logarithm of a call: the metrics call with 8 .. 32 rows of 1000 columns.
 // The bits of psum / plogp are a function of (n, K) and the sequence of calls.
 #include "igan_common.h"
+#include "class_argmax.h"      // cs_f4, cs_row_argmax: the row arg-max, shared with softmax_xent.hip
 
 namespace {
-
-typedef float cs_f4 __attribute__((ext_vector_type(4), aligned(4)));
 
 constexpr int CS_NT = 256;
 constexpr int CS_WAVES = CS_NT / 64;
 constexpr int CS_HIST_ROWS = 16;       // rows per workgroup of the histogram kernel: 4 per wavefront
 constexpr int CS_ROUND = 64;           // rows per round of the plogp workgroup: 16 per wavefront, one barrier pair per round
-constexpr int CS_NONE = 0x7fffffff;    // "no column yet"
-
-// a lane's running best, columns offered in ascending order
-__device__ inline void cs_offer(float v, int idx, float& bv, int& bi) {
-    const bool bnan = bv != bv;
-    if (bi == CS_NONE || (!bnan && (v != v || v > bv))) {
-        bv = v;
-        bi = idx;
-    }
-}
-
-// does (ov, oi) come before (bv, bi)?  NaN first, then the larger value (-0.0 == +0.0), then the lower index
-__device__ inline bool cs_beats(float ov, int oi, float bv, int bi) {
-    if (oi == CS_NONE) return false;
-    if (bi == CS_NONE) return true;
-    const bool onan = ov != ov, bnan = bv != bv;
-    if (onan != bnan) return onan;
-    if (!onan && ov != bv) return ov > bv;
-    return oi < bi;
-}
-
-__device__ inline int cs_row_argmax(const float* __restrict__ row, int K, int lane) {
-    float bv = -__builtin_huge_valf();
-    int bi = CS_NONE;
-    const int groups = K >> 2;
-    for (int g = lane; g < groups; g += 64) {
-        const cs_f4 v = *reinterpret_cast<const cs_f4*>(row + 4 * g);
-        cs_offer(v.x, 4 * g, bv, bi);
-        cs_offer(v.y, 4 * g + 1, bv, bi);
-        cs_offer(v.z, 4 * g + 2, bv, bi);
-        cs_offer(v.w, 4 * g + 3, bv, bi);
-    }
-    const int c = 4 * groups + lane;
-    if (lane < (K & 3)) cs_offer(row[c], c, bv, bi);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const float ov = __shfl_xor(bv, off, 64);
-        const int oi = __shfl_xor(bi, off, 64);
-        if (cs_beats(ov, oi, bv, bi)) {
-            bv = ov;
-            bi = oi;
-        }
-    }
-    return bi;
-}
-
 __global__ __launch_bounds__(CS_NT) void class_hist_kernel(const float* __restrict__ X, unsigned long long* __restrict__ counts,
                                                            int* __restrict__ labels, int n, int K) {
     __shared__ int lab[CS_HIST_ROWS];

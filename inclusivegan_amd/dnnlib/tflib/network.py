@@ -52,6 +52,9 @@ def find_var_owner(var_or_global_name):
     raise KeyError('set_vars: no live network has a variable %r' % name)
 
 
+_OWN_BUILD_MODULES = ('inclusivegan_amd.training.networks_classifier',)     # build-function modules the reference does not have
+
+
 def _resolve(func_name):
     if callable(func_name):
         return func_name
@@ -508,6 +511,8 @@ class Network:
         text of the reference module that defines the build function (training/networks_stylegan2.py of a reference
         checkout) when the pickle is meant to be opened BY the reference; '' when it only has to come back here."""
         fn = build_func_name or self._build_func_name.rsplit('.', 1)[-1]
+        if build_func_name is None and self._build_func_name.rsplit('.', 1)[0] in _OWN_BUILD_MODULES:
+            fn = self._build_func_name      # no counterpart in the reference: the dotted name, which network_from_state resolves as it stands
         return dict(version=4, name=self.name, static_kwargs=dict(self.static_kwargs),
                     components={k: c for k, c in self.components.items() if isinstance(c, Network)},
                     build_module_src=build_module_src, build_func_name=fn,

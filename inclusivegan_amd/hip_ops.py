@@ -2586,6 +2586,126 @@ class ClassHistogram:
         return self.counts.cpu().numpy()
 
 
+# ---- softmax cross-entropy (csrc/softmax_xent.hip; the Stacked-MNIST mode classifier's loss) -----------------------------------
+def _require_xent_rows(name, logits, labels):
+    _require_rows_f32(name, logits)
+    if not labels.is_cuda:
+        raise RuntimeError('inclusivegan_amd kernels need tensors on a ROCm device (got %s); there is no CPU path' % labels.device)
+    if labels.dtype != torch.int32 or not labels.is_contiguous() or labels.device != logits.device or labels.numel() != logits.shape[0]:
+        raise TypeError('%s: labels must be a contiguous int32 [n] tensor on the device of the logits (got %s %s on %s)'
+                        % (name, labels.dtype, tuple(labels.shape), labels.device))
+
+
+def softmax_xent_raw(logits, labels, return_pred=True):
+    """(loss [n] fp32, lse [n] fp64, pred [n] int32 or None) of logits [n, K] fp32 against labels [n] int32
+    (igan_softmax_xent_fwd): F.cross_entropy(reduction='none') evaluated in fp64 and rounded once, np.argmax per row; a label
+    outside [0, K) ignores its row (loss 0).  No synchronisation; n * K * 4 below 2 GiB per call."""
+    lib = _abi.get_plugin()
+    _require_xent_rows('softmax_xent', logits, labels)
+    n, K = (int(v) for v in logits.shape)
+    loss = torch.empty(n, device=logits.device, dtype=torch.float32)
+    lse = torch.empty(n, device=logits.device, dtype=torch.float64)
+    pred = torch.empty(n, device=logits.device, dtype=torch.int32) if return_pred else None
+    _abi.check(lib.igan_softmax_xent_fwd(_stream(), _ptr(logits), _ptr(labels), _ptr(loss), _ptr(lse), _ptr(pred), n, K))
+    return loss, lse, pred
+
+
+def softmax_xent_bwd_raw(logits, labels, lse, dloss):
+    """dlogits [n, K] fp32 = dloss_i * (softmax(logits)_ik - [k == label_i]) from the stored fp64 lse (igan_softmax_xent_bwd);
+    the rows of ignored labels are 0."""
+    lib = _abi.get_plugin()
+    _require_xent_rows('softmax_xent_bwd', logits, labels)
+    _require_cuda_f32(dloss)
+    _require_cuda_f64('softmax_xent_bwd', lse)
+    n, K = (int(v) for v in logits.shape)
+    if lse.numel() != n or dloss.numel() != n:
+        raise ValueError('softmax_xent_bwd: lse and dloss must be [n] for logits [n, K]')
+    dloss = dloss.contiguous()
+    dlogits = torch.empty_like(logits)
+    _abi.check(lib.igan_softmax_xent_bwd(_stream(), _ptr(logits), _ptr(labels), _ptr(lse), _ptr(dloss), _ptr(dlogits), n, K))
+    return dlogits
+
+
+def xent_stats_update_raw(loss, labels, pred, loss_sum, counts, K):
+    """loss_sum [1] fp64 += sum of loss over the rows whose label lies in [0, K), counts [2] int64 += (rows counted, rows
+    with pred == label) (igan_xent_stats_update: row order, one owner, no atomic).  In place, no synchronisation."""
+    lib = _abi.get_plugin()
+    _require_cuda_f32(loss)
+    _require_cuda_f64('xent_stats_update', loss_sum)
+    n = int(loss.numel())
+    for t, dtype, size, what in ((labels, torch.int32, n, 'labels: int32 [n]'), (pred, torch.int32, n, 'pred: int32 [n]'),
+                                 (counts, torch.int64, 2, 'counts: int64 [2]')):
+        if not t.is_cuda:
+            raise RuntimeError('inclusivegan_amd kernels need tensors on a ROCm device (got %s); there is no CPU path' % t.device)
+        if t.dtype != dtype or not t.is_contiguous() or t.device != loss.device or t.numel() != size:
+            raise TypeError('xent_stats_update: %s, contiguous, on the device of the loss (got %s %s on %s)' % (what, t.dtype, tuple(t.shape), t.device))
+    if not loss.is_contiguous() or loss_sum.numel() != 1 or loss_sum.device != loss.device:
+        raise ValueError('xent_stats_update: loss must be contiguous and loss_sum [1] on its device')
+    _abi.check(lib.igan_xent_stats_update(_stream(), _ptr(loss), _ptr(labels), _ptr(pred), _ptr(loss_sum), _ptr(counts), n, int(K)))
+
+
+class _SoftmaxXentGradFn(torch.autograd.Function):
+    """The backward kernel as a node of its own, so that differentiating it again is an error and not a silent zero."""
+
+    @staticmethod
+    def forward(ctx, dloss, logits, labels, lse):
+        return softmax_xent_bwd_raw(logits, labels, lse, dloss)
+
+    @staticmethod
+    def backward(ctx, g):
+        raise NotImplementedError('softmax cross-entropy: second-order gradients are not built (the classifier loss is first-order)')
+
+
+class SoftmaxXentFn(torch.autograd.Function):
+    """Per-row softmax cross-entropy of logits [n, K] fp32 against labels [n] int32 on the device: returns (loss [n] fp32,
+    pred [n] int32); a label outside [0, K) ignores its row.  lse is kept in fp64 for the backward kernel."""
+
+    @staticmethod
+    def forward(ctx, logits, labels):
+        logits = logits.contiguous()
+        loss, lse, pred = softmax_xent_raw(logits, labels)
+        ctx.save_for_backward(logits, labels, lse)
+        ctx.mark_non_differentiable(pred)
+        return loss, pred
+
+    @staticmethod
+    def backward(ctx, g, _g_pred):
+        logits, labels, lse = ctx.saved_tensors
+        if torch.is_grad_enabled():
+            return _SoftmaxXentGradFn.apply(g, logits, labels, lse), None
+        return softmax_xent_bwd_raw(logits, labels, lse, g), None
+
+
+class XentStats:
+    """Mean loss and accuracy of a stream of classifier steps, kept on the device.  update(loss, labels, pred) folds a step's
+    rows (igan_xent_stats_update) and synchronises nothing; to_host() is the one device -> host copy -> (mean loss, accuracy)
+    over the counted rows (NaN for none); reset() starts the next tick."""
+
+    def __init__(self, K, device):
+        K = int(K)
+        if K < 1:
+            raise ValueError('XentStats: K must be positive (got %d)' % K)
+        self.K, self.device = K, torch.device(device)
+        self.loss_sum = torch.zeros(1, device=self.device, dtype=torch.float64)
+        self.counts = torch.zeros(2, device=self.device, dtype=torch.int64)
+
+    def update(self, loss, labels, pred):
+        xent_stats_update_raw(loss.detach(), labels, pred, self.loss_sum, self.counts, self.K)
+
+    def reset(self):
+        self.loss_sum.zero_()
+        self.counts.zero_()
+
+    def sums(self):
+        """(loss sum, rows counted, rows correct) on the host."""
+        both = torch.cat([self.loss_sum, self.counts.to(torch.float64)]).cpu().numpy()     # counts < 2^53: exact
+        return float(both[0]), int(both[1]), int(both[2])
+
+    def to_host(self):
+        loss_sum, counted, correct = self.sums()
+        return (loss_sum / counted, correct / counted) if counted else (float('nan'), float('nan'))
+
+
 def split_bounds(num_images, num_splits):
     """(begin, end) of every split of metrics/inception_score.py:50-51: split s holds rows s N // S .. (s + 1) N // S."""
     num_images, num_splits = int(num_images), int(num_splits)

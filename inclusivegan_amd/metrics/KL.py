@@ -1,12 +1,12 @@
 """KL divergence of the generated Stacked-MNIST class histogram from the uniform distribution (reference: metrics/KL.py:20-52):
     density_fake = histogram(labels, bins = 0..K, density=True);  KL = sum_{p > 0} p * log(p / (1 / K)).
-Classifier injected as in mode_counts; float32 device logits are folded into a class histogram on the device and the
+Classifier injected, or picked up from `classifier_pkl`, as in mode_counts; float32 device logits are folded into a class histogram on the device and the
 divergence is taken from the K counts (`kl_from_counts`, bit for bit `kl_to_uniform` of the labels behind them).  Under a
 process group every rank folds its share and the counts are summed exactly (mode_counts.merged_class_counts)."""
 import numpy as np
 
 from . import metric_base
-from .mode_counts import class_statistics, merged_class_counts, predicted_labels  # noqa: F401  (predicted_labels: the host statement, kept importable)
+from .mode_counts import DEFAULT_CLASSIFIER_PKL, class_statistics, merged_class_counts, predicted_labels  # noqa: F401  (predicted_labels: the host statement, kept importable)
 
 
 def kl_to_uniform(labels_all, num_classes):
@@ -30,11 +30,12 @@ def kl_from_counts(counts):
 class KL(metric_base.MetricBase):
     multi_rank = True
 
-    def __init__(self, num_images, minibatch_per_gpu, classify_fn=None, **kwargs):
+    def __init__(self, num_images, minibatch_per_gpu, classify_fn=None, classifier_pkl=DEFAULT_CLASSIFIER_PKL, **kwargs):
         super().__init__(**kwargs)
         self.num_images = num_images
         self.minibatch_per_gpu = minibatch_per_gpu
         self.classify_fn = classify_fn
+        self.classifier_pkl = classifier_pkl
 
     def _evaluate(self, Gs, Gs_kwargs, num_gpus):
         import torch

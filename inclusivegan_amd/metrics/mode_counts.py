@@ -1,6 +1,7 @@
 """Number of Stacked-MNIST modes covered by the generator (reference: metrics/mode_counts.py:20-49): classify `num_images`
 fakes into the 1000 digit triples and count the distinct classes hit.  The classifier (metrics/stacked_mnist_classifier.pkl
-in the reference) is injected: `classify_fn(float images [n, C, H, W] in [-1, 1]) -> logits [n, K]`.
+in the reference) is injected: `classify_fn(float images [n, C, H, W] in [-1, 1]) -> logits [n, K]`; without one, the pickle
+this project's own trainer wrote at `classifier_pkl` (train_classifier.py, the reference's path by default) is picked up.
 
 Logits that come back as float32 device tensors stay on the device: every minibatch is folded into a
 `hip_ops.ClassHistogram` (csrc/class_stats.hip: np.argmax per row, 64-bit integer counts) and the K counts are the one device
@@ -17,10 +18,27 @@ import numpy as np
 from . import metric_base
 
 
+DEFAULT_CLASSIFIER_PKL = 'metrics/stacked_mnist_classifier.pkl'      # the reference's path (:29), relative to the working directory
+
+
+def _resolve_classifier(metric):
+    """An injected classify_fn always wins; without one, the pickle train_classifier wrote at metric.classifier_pkl is loaded
+    (once per metric object); without either, the error."""
+    import os
+    if metric.classify_fn is not None:
+        return
+    pkl = getattr(metric, 'classifier_pkl', None)
+    if pkl and os.path.isfile(pkl):
+        from ..train_classifier import load_classify_fn
+        metric.classify_fn = load_classify_fn(pkl)
+        return
+    raise RuntimeError('%s needs classify_fn: the reference\'s metrics/stacked_mnist_classifier.pkl is not available in this tree. '
+                       'Train this project\'s own classifier with `python -m inclusivegan_amd.train_classifier`.' % metric.name)
+
+
 def predicted_labels(metric, Gs, Gs_kwargs, num_gpus):
     import torch
-    if metric.classify_fn is None:
-        raise RuntimeError('%s needs classify_fn: the reference\'s metrics/stacked_mnist_classifier.pkl is not available in this tree' % metric.name)
+    _resolve_classifier(metric)
     minibatch_size = num_gpus * metric.minibatch_per_gpu
     labels_all = np.empty([metric.num_images], dtype=np.float32)
     num_classes = None
@@ -56,8 +74,7 @@ def class_statistics(metric, Gs, Gs_kwargs, num_gpus):
     integers, None, K); anything else is labelled on the host as there -> (None, labels_all, K)."""
     import torch
     from .. import hip_ops
-    if metric.classify_fn is None:
-        raise RuntimeError('%s needs classify_fn: the reference\'s metrics/stacked_mnist_classifier.pkl is not available in this tree' % metric.name)
+    _resolve_classifier(metric)
     minibatch_size = num_gpus * metric.minibatch_per_gpu
     hist = labels_all = num_classes = None
     for begin in range(0, metric.num_images, minibatch_size):
@@ -83,8 +100,7 @@ def shard_histogram(metric, Gs, Gs_kwargs, rank, world):
     """hip_ops.ClassHistogram of the fakes rank `rank` of `world` owns, or None when it owns none -- a function of its
     arguments alone (MetricBase._fold_shard_fakes), so one process can rebuild every rank's state."""
     from .. import hip_ops
-    if metric.classify_fn is None:
-        raise RuntimeError('%s needs classify_fn: the reference\'s metrics/stacked_mnist_classifier.pkl is not available in this tree' % metric.name)
+    _resolve_classifier(metric)
     state = []
 
     def fold(begin, end, images):
@@ -116,11 +132,12 @@ def merged_class_counts(metric, Gs, Gs_kwargs):
 class mode_counts(metric_base.MetricBase):
     multi_rank = True
 
-    def __init__(self, num_images, minibatch_per_gpu, classify_fn=None, **kwargs):
+    def __init__(self, num_images, minibatch_per_gpu, classify_fn=None, classifier_pkl=DEFAULT_CLASSIFIER_PKL, **kwargs):
         super().__init__(**kwargs)
         self.num_images = num_images
         self.minibatch_per_gpu = minibatch_per_gpu
         self.classify_fn = classify_fn
+        self.classifier_pkl = classifier_pkl
 
     def _evaluate(self, Gs, Gs_kwargs, num_gpus):
         import torch
