@@ -19,6 +19,7 @@
 //             block, per-block partials go to a caller workspace and a second tiny kernel adds them
 //             in fixed order (bit-reproducible; no float atomics).
 #include "igan_common.h"
+#include "fixed_order_sum.h"
 
 namespace {
 
@@ -72,8 +73,8 @@ __global__ __launch_bounds__(256) void ban_bwd_kernel(BanArgs a) {
     __shared__ float4 red[256];
     __shared__ float reds[256];
     const int cv = a.C >> 2;
-    const int cvt = min(cv, 256);               // columns handled by this block
-    const int rl = 256 / cvt;                   // row lanes
+    const igan::RowLanes L = igan::row_lanes(a.C);
+    const int cvt = L.cvt, rl = L.rl;           // columns handled by this block, row lanes
     const int col = threadIdx.x % cvt + blockIdx.y * 256;   // float4 column
     const int lane_r = threadIdx.x / cvt;
     const bool active = (col < cv) && (lane_r < rl);
@@ -118,25 +119,11 @@ __global__ __launch_bounds__(256) void ban_bwd_kernel(BanArgs a) {
     red[threadIdx.x] = accb;
     reds[threadIdx.x] = accs;
     __syncthreads();
-    // fold row lanes (fixed order)
-    if (threadIdx.x < cvt && col < cv) {
-        float4 t = red[threadIdx.x];
-        for (int j = 1; j < rl; j++) {
-            const float4 u = red[threadIdx.x + j * cvt];
-            t.x += u.x; t.y += u.y; t.z += u.z; t.w += u.w;
-        }
-        float* p = a.partial + (size_t)blockIdx.x * (a.C + 1) + (size_t)col * 4;
-        p[0] = t.x; p[1] = t.y; p[2] = t.z; p[3] = t.w;
-    }
+    if (threadIdx.x < cvt && col < cv)
+        igan::row_lane_fold<1>({red}, L, {a.partial + (size_t)blockIdx.x * (a.C + 1) + (size_t)col * 4});
     if (a.noise && blockIdx.y == 0) {
-        // block sum of accs in fixed order: wave shuffle tree then 4 waves
-        float s = reds[threadIdx.x];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-        __syncthreads();
-        if ((threadIdx.x & 63) == 0) reds[threadIdx.x >> 6] = s;
-        __syncthreads();
-        if (threadIdx.x == 0) a.partial[(size_t)blockIdx.x * (a.C + 1) + a.C] = (reds[0] + reds[1]) + (reds[2] + reds[3]);
+        const float tot = igan::block_sum_256<true>(reds[threadIdx.x], reds);
+        if (threadIdx.x == 0) a.partial[(size_t)blockIdx.x * (a.C + 1) + a.C] = tot;
     } else if (!a.noise && blockIdx.y == 0 && threadIdx.x == 0) {
         a.partial[(size_t)blockIdx.x * (a.C + 1) + a.C] = 0.f;
     }
@@ -148,25 +135,8 @@ __global__ __launch_bounds__(256) void ban_bwd_kernel(BanArgs a) {
 __global__ __launch_bounds__(256) void ban_final_kernel(const float* partial, float* db, float* dstrength, int blocks, int C) {
     __shared__ float red[256];
     const int c = blockIdx.x * 16 + (threadIdx.x & 15);
-    const int grp = threadIdx.x >> 4;
-    float s = 0.f;
-    if (c <= C) {
-        // four independent partial sums: four loads in flight per lane instead of a chain of dependent L2 round trips
-        float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-        int j = grp;
-        for (; j + 48 < blocks; j += 64) {
-            s0 += partial[(size_t)j * (C + 1) + c];        s1 += partial[(size_t)(j + 16) * (C + 1) + c];
-            s2 += partial[(size_t)(j + 32) * (C + 1) + c]; s3 += partial[(size_t)(j + 48) * (C + 1) + c];
-        }
-        for (; j < blocks; j += 16) s0 += partial[(size_t)j * (C + 1) + c];
-        s = (s0 + s1) + (s2 + s3);
-    }
-    red[threadIdx.x] = s;
-    __syncthreads();
-    if (grp == 0 && c <= C) {
-        float t = 0.f;
-#pragma unroll
-        for (int g = 0; g < 16; g++) t += red[g * 16 + threadIdx.x];
+    const float t = igan::column_fold_16x16(partial, C + 1, 0, blocks, c, c <= C, red);
+    if (threadIdx.x < 16 && c <= C) {
         if (c < C) { if (db) db[c] = t; }
         else if (dstrength) *dstrength = t;
     }
@@ -183,8 +153,8 @@ __global__ __launch_bounds__(256) void ban_bwd_dd_kernel(BanArgs a, const float*
     __shared__ float4 red2[256];
     __shared__ float reds[256];
     const int cv = a.C >> 2;
-    const int cvt = min(cv, 256);
-    const int rl = 256 / cvt;
+    const igan::RowLanes L = igan::row_lanes(a.C);
+    const int cvt = L.cvt, rl = L.rl;
     const int col = threadIdx.x % cvt + blockIdx.y * 256;
     const int lane_r = threadIdx.x / cvt;
     const bool active = (col < cv) && (lane_r < rl);
@@ -241,25 +211,12 @@ __global__ __launch_bounds__(256) void ban_bwd_dd_kernel(BanArgs a, const float*
     __syncthreads();
     const int W = 2 * a.C + 1;
     if (threadIdx.x < cvt && col < cv) {
-        float4 t = red[threadIdx.x], t2 = red2[threadIdx.x];
-        for (int k = 1; k < rl; k++) {
-            const float4 u = red[threadIdx.x + k * cvt], u2 = red2[threadIdx.x + k * cvt];
-            t.x += u.x; t.y += u.y; t.z += u.z; t.w += u.w;
-            t2.x += u2.x; t2.y += u2.y; t2.z += u2.z; t2.w += u2.w;
-        }
         float* p = a.partial + (size_t)blockIdx.x * W + (size_t)col * 4;
-        p[0] = t.x; p[1] = t.y; p[2] = t.z; p[3] = t.w;
-        float* q = p + a.C + 1;
-        q[0] = t2.x; q[1] = t2.y; q[2] = t2.z; q[3] = t2.w;
+        igan::row_lane_fold<2>({red, red2}, L, {p, p + a.C + 1});
     }
     if (blockIdx.y == 0) {
-        float s = a.noise ? reds[threadIdx.x] : 0.f;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-        __syncthreads();
-        if ((threadIdx.x & 63) == 0) reds[threadIdx.x >> 6] = s;
-        __syncthreads();
-        if (threadIdx.x == 0) a.partial[(size_t)blockIdx.x * W + a.C] = (reds[0] + reds[1]) + (reds[2] + reds[3]);
+        const float tot = igan::block_sum_256<true>(a.noise ? reds[threadIdx.x] : 0.f, reds);
+        if (threadIdx.x == 0) a.partial[(size_t)blockIdx.x * W + a.C] = tot;
     }
 }
 
@@ -270,29 +227,13 @@ __global__ __launch_bounds__(256) void ban_dd_final_kernel(const float* partial,
     __shared__ float red[256];
     const int W = 2 * C + 1;
     const int c = blockIdx.x * 16 + (threadIdx.x & 15);
-    const int grp = threadIdx.x >> 4;
     const bool sample = blockIdx.y > 0;
     const int n = (int)blockIdx.y - 1;
     const int b0 = sample ? n * bps : 0, b1 = sample ? (n + 1) * bps : N * bps;
     const int off = sample ? C + 1 : 0;
     const int cmax = sample ? C - 1 : C;
-    float s = 0.f;
-    if (c <= cmax) {
-        float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-        int j = b0 + grp;
-        for (; j + 48 < b1; j += 64) {
-            s0 += partial[(size_t)j * W + off + c];        s1 += partial[(size_t)(j + 16) * W + off + c];
-            s2 += partial[(size_t)(j + 32) * W + off + c]; s3 += partial[(size_t)(j + 48) * W + off + c];
-        }
-        for (; j < b1; j += 16) s0 += partial[(size_t)j * W + off + c];
-        s = (s0 + s1) + (s2 + s3);
-    }
-    red[threadIdx.x] = s;
-    __syncthreads();
-    if (grp == 0 && c <= cmax) {
-        float t = 0.f;
-#pragma unroll
-        for (int g = 0; g < 16; g++) t += red[g * 16 + threadIdx.x];
+    const float t = igan::column_fold_16x16(partial, W, b0, b1, off + c, c <= cmax, red);
+    if (threadIdx.x < 16 && c <= cmax) {
         if (sample) { if (dd) dd[(size_t)n * C + c] = t / dscale[(size_t)n * C + c]; }
         else if (c < C) { if (db) db[c] = t; }
         else if (dstrength) *dstrength = t;
@@ -300,18 +241,13 @@ __global__ __launch_bounds__(256) void ban_dd_final_kernel(const float* partial,
 }
 
 int ban_dd_bps(int N, int HW, int C) {
-    const int cvt = std::min(C / 4, 256);
-    const int rl = 256 / cvt;
     // aim for >= 8 rows per row-lane per block and about 512 blocks in all
-    return std::max(1, std::min(std::max(512 / std::max(N, 1), 1), std::max(HW / (rl * 8), 1)));
+    return std::max(1, std::min(std::max(512 / std::max(N, 1), 1), std::max(igan::row_lane_blocks(HW, C), 1)));
 }
 
 int ban_blocks(int rows, int C) {
-    const int cvt = std::min(C / 4, 256);
-    const int rl = 256 / cvt;
     // aim for >= 8 rows per row-lane per block, at most 512 blocks
-    int b = rows / (rl * 8);
-    return std::max(1, std::min(b, 512));
+    return std::max(1, std::min(igan::row_lane_blocks(rows, C), 512));
 }
 
 int ban_check(const char* who, int rows, int C, int act, float gain) {
@@ -379,6 +315,7 @@ extern "C" int igan_bias_act_noise_bwd(igan_stream_t stream_, const float* dy, c
     IGAN_REQUIRE(dy && y && dx && workspace, "bias_act_noise_bwd: null buffer");
     IGAN_REQUIRE((noise == nullptr) || (dstrength != nullptr), "bias_act_noise_bwd: noise given without dstrength");
     if (int rc = ban_check("bias_act_noise_bwd", rows, C, act, gain)) return rc;
+    IGAN_REQUIRE(noise == nullptr || C <= 1024, "bias_act_noise_bwd: with noise C must be <= 1024 (the noise-strength partial is reduced by the first block column only)");
     IGAN_REQUIRE((((uintptr_t)dy | (uintptr_t)y | (uintptr_t)dx) & 15) == 0, "bias_act_noise_bwd: buffers must be 16-byte aligned");
     BanArgs a{dy, y, noise, nullptr, nullptr, dx, workspace, rows, C, act, alpha, gain};
     const int blocks = ban_blocks(rows, C);

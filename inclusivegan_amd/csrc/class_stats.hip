@@ -25,6 +25,7 @@
 //              One compute unit evaluates every logarithm of a call: the metrics call with 8 .. 32 rows of 1000 columns.
 // The bits of psum / plogp are a function of (n, K) and the sequence of calls.
 #include "igan_common.h"
+#include "fixed_order_sum.h"
 #include "class_argmax.h"      // cs_f4, cs_row_argmax: the row arg-max, shared with softmax_xent.hip
 
 namespace {
@@ -97,8 +98,7 @@ __global__ __launch_bounds__(CS_NT) void prob_stats_kernel(const float* __restri
                 s += cs_plogp(v.w);
             }
             if (lane < (K & 3)) s += cs_plogp(row[4 * groups + lane]);
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+            s = igan::wave_sum(s);
             if (lane == 0) rowsum[r] = s;
         }
         __syncthreads();

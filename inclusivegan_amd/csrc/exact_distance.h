@@ -5,6 +5,7 @@
 // procedure built on them is exact_search.h.
 #pragma once
 #include "igan_common.h"
+#include "fixed_order_sum.h"
 #include <cmath>
 
 namespace igan {
@@ -62,10 +63,7 @@ __device__ __forceinline__ double wave_sqdist(const float* __restrict__ a, const
             s0 += d * d;
         }
     }
-    double s = s0 + s1;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
-    return s;
+    return wave_sum(s0 + s1);
 }
 
 // The [nq x dim] x [dim x nc] product q.c of a query batch and a candidate batch on the exact-fp32 MFMA: a 1x1 convolution with the

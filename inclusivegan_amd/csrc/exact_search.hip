@@ -45,8 +45,7 @@ __global__ __launch_bounds__(256) void row_sqnorm_kernel(const float* a, float* 
         const double v = (double)p[i];
         s += v * v;
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+    s = wave_sum_lane0(s);
     if (lane == 0) out[wave] = (float)s;
 }
 

@@ -10,6 +10,7 @@
 // maps to four consecutive bias entries and the bias load is one (L1/L2-resident)
 // float4 as well.
 #include "igan_common.h"
+#include "fixed_order_sum.h"
 #include <hip/hip_fp16.h>
 
 namespace {
@@ -171,16 +172,7 @@ __global__ __launch_bounds__(256) void bias_grad_rows_kernel(const float* dx, fl
     const int r0 = blockIdx.y * BG_ROWS_PER_BLOCK;
     const int r1 = min(r0 + BG_ROWS_PER_BLOCK, rows);
     if (c >= sizeB) return;
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-    int r = r0;
-    for (; r + 3 < r1; r += 4) {
-        s0 += dx[(long long)(r + 0) * sizeB + c];
-        s1 += dx[(long long)(r + 1) * sizeB + c];
-        s2 += dx[(long long)(r + 2) * sizeB + c];
-        s3 += dx[(long long)(r + 3) * sizeB + c];
-    }
-    for (; r < r1; r++) s0 += dx[(long long)r * sizeB + c];
-    partial[(long long)blockIdx.y * sizeB + c] = (s0 + s1) + (s2 + s3);
+    partial[(long long)blockIdx.y * sizeB + c] = igan::serial_sum4(dx, sizeB, r0, r1, c);
 }
 
 // general stepB (> 1): one block per (outer index, channel): wave-shuffle + LDS tree.
@@ -190,26 +182,15 @@ __global__ __launch_bounds__(256) void bias_grad_planes_kernel(const float* dx, 
     const float* src = dx + ((long long)o * sizeB + c) * stepB;
     float s = 0.f;
     for (int i = threadIdx.x; i < stepB; i += blockDim.x) s += src[i];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
     __shared__ float red[4];
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) partial[(long long)o * sizeB + c] = (red[0] + red[1]) + (red[2] + red[3]);
+    const float tot = igan::block_sum_256(s, red);
+    if (threadIdx.x == 0) partial[(long long)o * sizeB + c] = tot;
 }
 
 __global__ __launch_bounds__(256) void bias_grad_final_kernel(const float* partial, float* db, int chunks, int sizeB) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= sizeB) return;
-    // four partial sums (fixed order): four loads in flight instead of `chunks` dependent L2 round trips
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-    int j = 0;
-    for (; j + 4 <= chunks; j += 4) {
-        s0 += partial[(long long)j * sizeB + c];       s1 += partial[(long long)(j + 1) * sizeB + c];
-        s2 += partial[(long long)(j + 2) * sizeB + c]; s3 += partial[(long long)(j + 3) * sizeB + c];
-    }
-    for (; j < chunks; j++) s0 += partial[(long long)j * sizeB + c];
-    db[c] = (s0 + s1) + (s2 + s3);
+    db[c] = igan::serial_sum4(partial, sizeB, 0, chunks, c);
 }
 
 int bias_grad_chunks(int sizeX, int sizeB, int stepB) {

@@ -11,20 +11,11 @@
 // slice's partial statistic, and the consumer adds the slices in fixed order.  A second kernel writes the
 // concatenated [N,H,W,C+1] output (row stride C+1 is odd, so scalar accesses).
 #include "igan_common.h"
+#include "fixed_order_sum.h"
 
 namespace {
 
 constexpr int MB_MAXG = 16;
-
-__device__ __forceinline__ float block_sum_256(float s, float* red) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    const float r = (red[0] + red[1]) + (red[2] + red[3]);
-    __syncthreads();
-    return r;
-}
 
 constexpr int MB_MAXS = 64;     // slices of the position axis
 
@@ -54,7 +45,8 @@ __global__ __launch_bounds__(256) void mbstd_stat_kernel(const float* x, float* 
         var /= (float)G;
         s += sqrtf(var + 1e-8f);
     }
-    const float tot = block_sum_256(s, red);
+    const float tot = igan::block_sum_256(s, red);
+    __syncthreads();
     if (threadIdx.x == 0) partial[m * S + blockIdx.y] = tot;
 }
 
@@ -89,7 +81,8 @@ __global__ __launch_bounds__(256) void mbstd_bwd_kernel(const float* x, const fl
         const int pix = i - g * HW;
         s += dy[(((long long)(g * M + m)) * HW + pix) * (C + 1) + C];
     }
-    const float dstat = block_sum_256(s, red);
+    const float dstat = igan::block_sum_256(s, red);
+    __syncthreads();
     const float scale = dstat / ((float)G * (float)P);
     for (int p = p0 + threadIdx.x; p < p1; p += blockDim.x) {
         const int pix = p / C;

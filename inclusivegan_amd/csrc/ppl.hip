@@ -12,10 +12,13 @@
 //                        strides it has, written channel-minor for the VGG convolutions.
 // Both are streaming kernels: 16-byte accesses where the addresses allow them, nothing staged.
 #include "igan_common.h"
+#include "fixed_order_sum.h"
 
 #include <cmath>
 
 namespace {
+
+using igan::wave_sum;
 
 // ---------------------------------------------------------------------------------------------------------------------
 // lerp
@@ -60,11 +63,6 @@ __global__ __launch_bounds__(256) void ppl_lerp_kernel(const float* __restrict__
 // ---------------------------------------------------------------------------------------------------------------------
 // slerp
 
-__device__ __forceinline__ double wave_sum(double s) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
-    return s;
-}
 
 // The lane's share of one pair's two rows.  each(f) calls f(a_j, b_j) for every element j < dim the lane owns;
 // each_store(g) does the same with g(a_j, b_j, o0, o1) and writes o0 to the row at t, o1 to the row at t + epsilon.

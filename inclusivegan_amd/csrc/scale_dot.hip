@@ -11,6 +11,7 @@
 // (out may alias b).  Same thread layout as the fused epilogue backward (row lanes x float4 columns,
 // column sums in registers, LDS fold, per-block partials, fixed-order final add: deterministic).
 #include "igan_common.h"
+#include "fixed_order_sum.h"
 
 namespace {
 
@@ -26,8 +27,8 @@ struct SdArgs {
 __global__ __launch_bounds__(256) void scale_dot_kernel(SdArgs p) {
     __shared__ float4 red[256];
     const int cv = p.C >> 2;
-    const int cvt = min(cv, 256);
-    const int rl = 256 / cvt;
+    const igan::RowLanes L = igan::row_lanes(p.C);
+    const int cvt = L.cvt, rl = L.rl;
     const int col = threadIdx.x % cvt + blockIdx.z * 256;
     const int lane_r = threadIdx.x / cvt;
     const int n = blockIdx.y;
@@ -65,44 +66,17 @@ __global__ __launch_bounds__(256) void scale_dot_kernel(SdArgs p) {
     }
     red[threadIdx.x] = acc;
     __syncthreads();
-    if (threadIdx.x < cvt && col < cv) {
-        float4 t = red[threadIdx.x];
-        for (int j = 1; j < rl; j++) {
-            const float4 u = red[threadIdx.x + j * cvt];
-            t.x += u.x; t.y += u.y; t.z += u.z; t.w += u.w;
-        }
-        float* q = p.partial + ((size_t)n * p.blocks + blockIdx.x) * p.C + (size_t)col * 4;
-        q[0] = t.x; q[1] = t.y; q[2] = t.z; q[3] = t.w;
-    }
+    if (threadIdx.x < cvt && col < cv)
+        igan::row_lane_fold<1>({red}, L, {p.partial + ((size_t)n * p.blocks + blockIdx.x) * p.C + (size_t)col * 4});
 }
 
 // dot[n][c] = sum_j partial[n][j][c]; grid = (ceil(C/16), N), 16 columns x 16 groups.
 __global__ __launch_bounds__(256) void scale_dot_final_kernel(const float* partial, float* dot, int blocks, int C) {
     __shared__ float red[256];
     const int c = blockIdx.x * 16 + (threadIdx.x & 15);
-    const int grp = threadIdx.x >> 4;
     const int n = blockIdx.y;
-    float s = 0.f;
-    if (c < C) {
-        // four independent partial sums: four loads in flight per lane instead of a chain of dependent L2 round trips
-        const float* q = partial + (size_t)n * blocks * C + c;
-        float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-        int j = grp;
-        for (; j + 48 < blocks; j += 64) {
-            s0 += q[(size_t)j * C];        s1 += q[(size_t)(j + 16) * C];
-            s2 += q[(size_t)(j + 32) * C]; s3 += q[(size_t)(j + 48) * C];
-        }
-        for (; j < blocks; j += 16) s0 += q[(size_t)j * C];
-        s = (s0 + s1) + (s2 + s3);
-    }
-    red[threadIdx.x] = s;
-    __syncthreads();
-    if (grp == 0 && c < C) {
-        float t = 0.f;
-#pragma unroll
-        for (int g = 0; g < 16; g++) t += red[g * 16 + threadIdx.x];
-        dot[(size_t)n * C + c] = t;
-    }
+    const float t = igan::column_fold_16x16(partial + (size_t)n * blocks * C + c, C, 0, blocks, 0, c < C, red);
+    if (threadIdx.x < 16 && c < C) dot[(size_t)n * C + c] = t;
 }
 
 // out = a * alpha[n,c] + b * beta[n,c]: one pass where the second-order backward of the modulated convolution ran two or three
@@ -133,9 +107,7 @@ __global__ __launch_bounds__(256) void scale_add_kernel(const float4* a, const f
 }
 
 int sd_blocks(int N, int HW, int C) {
-    const int cvt = std::min(C / 4, 256);
-    const int rl = 256 / cvt;
-    int b = HW / (rl * 8);                       // >= 8 rows per row lane
+    const int b = igan::row_lane_blocks(HW, C);
     const int want = std::max(1, 1024 / std::max(N, 1));   // ~1024 blocks over the batch
     return std::max(1, std::min(b, want));
 }

@@ -25,6 +25,7 @@
 //              integer counts are summed over the workgroup (order-free) and added by thread 0.  No atomic of any kind.
 // The bits of every output are a function of (n, K), the data and the sequence of calls.
 #include "igan_common.h"
+#include "fixed_order_sum.h"
 #include "class_argmax.h"
 
 namespace {
@@ -58,8 +59,7 @@ __global__ __launch_bounds__(SX_NT) void softmax_xent_fwd_kernel(const float* __
         s += sx_term(v.w, m, 4 * g + 3 == best);
     }
     if (lane < (K & 3)) s += sx_term(row[4 * groups + lane], m, 4 * groups + lane == best);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+    s = igan::wave_sum(s);
     if (lane == 0) {
         const double l = m + log1p(s);
         const int lab = labels[r];
@@ -113,11 +113,8 @@ __global__ __launch_bounds__(SX_NT) void xent_stats_kernel(const float* __restri
         }
         __syncthreads();                      // the next round overwrites park
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        counted += __shfl_xor(counted, off, 64);
-        correct += __shfl_xor(correct, off, 64);
-    }
+    counted = igan::wave_sum(counted);
+    correct = igan::wave_sum(correct);
     if (lane == 0) {
         wsum[0][wave] = counted;
         wsum[1][wave] = correct;

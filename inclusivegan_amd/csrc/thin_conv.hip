@@ -12,6 +12,7 @@
 //              one sample's pixel range per workgroup, 16 accumulators per lane, fixed-order two-level reduce
 // Dispatched from igan_conv2d / igan_conv2d_wgrad (stride 1, up 1); everything else stays on the MFMA kernels.
 #include "igan_common.h"
+#include "fixed_order_sum.h"
 #include <cstdlib>
 
 namespace {
@@ -406,7 +407,7 @@ __global__ __launch_bounds__(256) void thin_wgrad_final_kernel(const float* part
     const int c = i / T, t = i - c * T;
     float s = 0.f;
     for (int b = lane; b < blocks; b += 64) s += partial[((size_t)b * C + c) * 4 + t];
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+    s = igan::wave_sum(s);
     if (lane == 0) dw[thin_is_out ? c * T + t : t * C + c] = s * alpha;
 }
 
