@@ -237,7 +237,10 @@ typedef struct igan_conv2d_params {
 int igan_conv2d_plan(const igan_conv2d_params* p, int* splits, int* sliced_tiles, size_t* workspace_floats);
 int igan_conv2d(igan_stream_t stream, const igan_conv2d_params* p);
 /* Host-only: name of the kernel instantiation igan_conv2d() launches for these parameters (as reported
- * by rocprofv3, minus the anonymous-namespace prefix).  For profiling tools. */
+ * by rocprofv3, minus the anonymous-namespace prefix).  For profiling tools.
+ * The thin-channel names carry the tap count only: "thin_out_kernel<1>" covers one and two channel blocks (thin_out_kernel<1, 1> and
+ * <1, 2>, Cin = 512), and "thin_in_kernel<9>" also stands for the sliding-window kernel thin_in3x3_kernel<3> that takes a 3x3 filter
+ * when Cin == 3, Cout <= 256 and OW >= 16. */
 int igan_conv2d_kernel_name(const igan_conv2d_params* p, char* buf, int buflen);
 
 /* Weight gradient of the op above (same geometry fields):
