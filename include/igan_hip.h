@@ -44,7 +44,7 @@ extern "C" {
  * igan_images_to_uint8, igan_images_from_uint8, igan_dense_small2_grouped, igan_dense_small_wgrad2_grouped, igan_rows_group_sum,
  * igan_scale_add, igan_kmeans_workspace_bytes, igan_kmeans_step, igan_moments_workspace_bytes, igan_moments_update, igan_moments_finalize,
  * igan_moments_merge, igan_class_hist_update, igan_prob_stats_update, igan_nnk_update, igan_softmax_xent_fwd, igan_softmax_xent_bwd,
- * igan_xent_stats_update). */
+ * igan_xent_stats_update, igan_sigmoid_xent_fwd, igan_sigmoid_xent_bwd, igan_sigmoid_xent_stats_update, igan_binary_probs). */
 #define IGAN_ABI_VERSION 10
 
 typedef void* igan_stream_t; /* hipStream_t */
@@ -681,6 +681,48 @@ int igan_softmax_xent_bwd(igan_stream_t stream, const float* logits /* [n][K] */
 int igan_xent_stats_update(igan_stream_t stream, const float* loss /* [n] */, const int* labels /* [n] */, const int* pred /* [n] */,
                            double* loss_sum /* [1], accumulated */, long long* counts /* [2]: rows counted, rows correct; accumulated */,
                            int n, int K);
+
+/* ------------------------------------------------------------------------
+ * Sigmoid (binary) cross-entropy against {0, 1} targets, A independent attributes per row: the loss of the CelebA attribute
+ * classifier this project trains for itself (the reference downloads 40 classifiers, metrics/linear_separability.py:20-61,
+ * from URLs this tree never opens), and the probability pairs linear separability takes from it.  Added without a version
+ * bump: four more exports, no struct or signature changes.  Arguments are validated before anything touches a device: a null
+ * pointer (pos_weight, and pred of the forward, may be NULL), n < 1, A < 1, n * A * 4 at or above 2 GiB, loss_sum / counts /
+ * probs not 8-byte aligned or another float buffer not 4-byte aligned return IGAN_ERR_INVALID_ARGUMENT.  Inputs are dense
+ * row-major and need 4-byte alignment ONLY: a row of an odd A starts anywhere.  No workspace, no floating-point atomic: the
+ * bits are a function of (n, A), the data and the sequence of calls.
+ *
+ * igan_sigmoid_xent_fwd / _bwd replace torch.nn.functional.binary_cross_entropy_with_logits(logits, targets,
+ * pos_weight=pos_weight, reduction='none') and its gradient, as fp64 states them.  With x = (double)logits[i][a],
+ * w = pos_weight[a] (1 when the pointer is NULL) and softplus(z) = max(z, 0) + log1p(exp(-|z|)) in fp64, by the element's target t:
+ *     t == 1.0f  positive    loss = (float)(w * softplus(-x))      dlogits = (float)(dloss * (-w / (1 + exp(x))))
+ *     t == 0.0f  negative    loss = (float)(softplus(x))           dlogits = (float)(dloss * (1 / (1 + exp(-x))))
+ *     otherwise  ignored     loss = 0                              dlogits = 0        (NaN and the trainer's padding -1 included)
+ *     pred[i][a] = x > 0                                                              (a NaN predicts 0)
+ * each result rounded to fp32 once.  The gradient is NOT sigmoid(x) - t: a confident correct element keeps every digit of its
+ * small gradient.  A NaN logit gives a NaN loss and gradient (the max is a comparison and does not swallow it); +infinity
+ * with a positive target gives loss 0 (softplus(-inf) = 0, never inf - inf) and gradient -0 * dloss, with a negative target
+ * loss +infinity.  A non-finite logit changes its own element only.  One thread per element.
+ *
+ * igan_sigmoid_xent_stats_update ACCUMULATES the numbers a trainer tick reports per attribute a, over the elements that are not ignored:
+ *     loss_sum[a] += sum_i (double)loss[i][a]   one owner per column, rows in ascending order, ONE fp64 accumulator
+ *     counts[a][0..3] += (tp, fp, tn, fn)        positive & pred, negative & pred, negative & !pred, positive & !pred, pred = logits > 0
+ * so the mean loss, accuracy and balanced accuracy of every attribute are one device -> host copy.  A NaN loss makes that
+ * column's loss_sum NaN, as the sum does.
+ *
+ * igan_binary_probs replaces softmax(concat([logits, -logits], axis=1)) of linear_separability.py:138 for ALL attributes of a
+ * [n][A] logit matrix in one pass:
+ *     probs[a][i][0] = (float)(1 / (1 + exp(-2 x)))      probs[a][i][1] = (float)(1 / (1 + exp(2 x)))      (x - (-x) = 2 x)
+ * attribute-major, so that attribute a's [n][2] block is contiguous.  fp64 from the fp32 logit, one rounding each; NaN gives
+ * (NaN, NaN), +infinity (1, 0). */
+int igan_sigmoid_xent_fwd(igan_stream_t stream, const float* logits /* [n][A] */, const float* targets /* [n][A] */,
+                          const float* pos_weight /* [A] or NULL */, float* loss /* [n][A] */, int8_t* pred /* [n][A] or NULL */, int n, int A);
+int igan_sigmoid_xent_bwd(igan_stream_t stream, const float* logits /* [n][A] */, const float* targets /* [n][A] */,
+                          const float* pos_weight /* [A] or NULL */, const float* dloss /* [n][A] */, float* dlogits /* [n][A] */, int n, int A);
+int igan_sigmoid_xent_stats_update(igan_stream_t stream, const float* loss /* [n][A] */, const float* logits /* [n][A] */,
+                                   const float* targets /* [n][A] */, double* loss_sum /* [A], accumulated */,
+                                   long long* counts /* [A][4]: tp, fp, tn, fn; accumulated */, int n, int A);
+int igan_binary_probs(igan_stream_t stream, const float* logits /* [n][A] */, float* probs /* [A][n][2] */, int n, int A);
 
 /* ------------------------------------------------------------------------
  * Perceptual path length (reference: metrics/perceptual_path_length.py; ppl_zfull .. ppl2_wend).  Added without a

@@ -216,6 +216,10 @@ SIGNATURES = {
     'igan_softmax_xent_fwd': (_I, [_P, _P, _P, _P, _P, _P, _I, _I]),
     'igan_softmax_xent_bwd': (_I, [_P, _P, _P, _P, _P, _P, _I, _I]),
     'igan_xent_stats_update': (_I, [_P, _P, _P, _P, _P, _P, _I, _I]),
+    'igan_sigmoid_xent_fwd': (_I, [_P, _P, _P, _P, _P, _P, _I, _I]),
+    'igan_sigmoid_xent_bwd': (_I, [_P, _P, _P, _P, _P, _P, _I, _I]),
+    'igan_sigmoid_xent_stats_update': (_I, [_P, _P, _P, _P, _P, _P, _I, _I]),
+    'igan_binary_probs': (_I, [_P, _P, _P, _I, _I]),
     'igan_ppl_endpoints': (_I, [_P, _P, _P, _P, _I, _I, ctypes.c_double, _I]),
     'igan_ppl_crop_prep': (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _LL, _LL, _LL, _LL]),
     'igan_linear_svc_workspace_bytes': (_SZ, [_I, _I, _I]),

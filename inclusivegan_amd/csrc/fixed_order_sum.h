@@ -131,4 +131,16 @@ __device__ __forceinline__ float serial_sum4(const float* p, int stride, int fir
     return (s0 + s1) + (s2 + s3);
 }
 
+// acc + the terms term(first), term(first + 1), ..., term(end - 1) by ONE thread with ONE fp64 accumulator that starts at acc:
+// (((acc + term(first)) + term(first + 1)) + ...) + term(end - 1), ascending, serially, one rounding per term.  `term` is called
+// once per j in that order and may keep counts of its own; a term that must not take part returns +0.0 (x + 0.0 == x for every
+// x but -0.0).  The loads behind `term` do not depend on the sum, so an unrolled loop keeps several in flight; the additions
+// stay one chain.
+template <typename F>
+__device__ __forceinline__ double serial_sum_f64(double acc, int first, int end, F term) {
+#pragma unroll 4
+    for (int j = first; j < end; j++) acc += term(j);
+    return acc;
+}
+
 }  // namespace igan

@@ -2706,6 +2706,155 @@ class XentStats:
         return (loss_sum / counted, correct / counted) if counted else (float('nan'), float('nan'))
 
 
+# ---- sigmoid cross-entropy (csrc/sigmoid_xent.hip; the CelebA attribute classifier's loss, linear separability's pairs) ---------
+def _require_bce_rows(name, logits, *same_shape, pos_weight=None):
+    """logits [n, A] and every tensor of `same_shape`: contiguous fp32 on one device, one shape; pos_weight [A] or None."""
+    _require_rows_f32(name, logits)
+    _require_cuda_f32(*same_shape, pos_weight)
+    for t in same_shape:
+        if tuple(t.shape) != tuple(logits.shape) or not t.is_contiguous() or t.device != logits.device:
+            raise ValueError('%s: targets / loss / dloss must be contiguous [n, A] tensors on the device of the logits %s (got %s on %s)'
+                             % (name, tuple(logits.shape), tuple(t.shape), t.device))
+    if pos_weight is not None and (pos_weight.numel() != logits.shape[1] or not pos_weight.is_contiguous() or pos_weight.device != logits.device):
+        raise ValueError('%s: pos_weight must be a contiguous [A] tensor on the device of the logits' % name)
+
+
+def sigmoid_xent_raw(logits, targets, pos_weight=None, return_pred=True):
+    """(loss [n, A] fp32, pred [n, A] int8 or None) of logits [n, A] fp32 against targets [n, A] fp32 (igan_sigmoid_xent_fwd):
+    F.binary_cross_entropy_with_logits(reduction='none', pos_weight=pos_weight [A]) evaluated in fp64 and rounded once,
+    pred = logits > 0; a target that is neither 1 nor 0 ignores its element (loss 0).  No synchronisation; n * A * 4 below 2 GiB
+    per call."""
+    lib = _abi.get_plugin()
+    _require_bce_rows('sigmoid_xent', logits, targets, pos_weight=pos_weight)
+    n, A = (int(v) for v in logits.shape)
+    loss = torch.empty_like(logits)
+    pred = torch.empty((n, A), device=logits.device, dtype=torch.int8) if return_pred else None
+    _abi.check(lib.igan_sigmoid_xent_fwd(_stream(), _ptr(logits), _ptr(targets), _ptr(pos_weight), _ptr(loss), _ptr(pred), n, A))
+    return loss, pred
+
+
+def sigmoid_xent_bwd_raw(logits, targets, dloss, pos_weight=None):
+    """dlogits [n, A] fp32 = dloss * (-w / (1 + exp(x))) at a positive, dloss / (1 + exp(-x)) at a negative, 0 at an ignored
+    element (igan_sigmoid_xent_bwd): fp64 from the fp32 logit, one rounding."""
+    lib = _abi.get_plugin()
+    _require_cuda_f32(dloss)
+    dloss = dloss.contiguous()
+    _require_bce_rows('sigmoid_xent_bwd', logits, targets, dloss, pos_weight=pos_weight)
+    n, A = (int(v) for v in logits.shape)
+    dlogits = torch.empty_like(logits)
+    _abi.check(lib.igan_sigmoid_xent_bwd(_stream(), _ptr(logits), _ptr(targets), _ptr(pos_weight), _ptr(dloss), _ptr(dlogits), n, A))
+    return dlogits
+
+
+def sigmoid_xent_stats_update_raw(loss, logits, targets, loss_sum, counts):
+    """loss_sum [A] fp64 += column sums of loss over the elements that are not ignored, counts [A, 4] int64 += (tp, fp, tn, fn)
+    with pred = logits > 0 (igan_sigmoid_xent_stats_update: one owner per column, row order, no atomic).  In place, no
+    synchronisation."""
+    lib = _abi.get_plugin()
+    _require_cuda_f32(loss)
+    _require_bce_rows('sigmoid_xent_stats_update', logits, loss, targets)
+    _require_cuda_f64('sigmoid_xent_stats_update', loss_sum)
+    n, A = (int(v) for v in logits.shape)
+    if not counts.is_cuda:
+        raise RuntimeError('inclusivegan_amd kernels need tensors on a ROCm device (got %s); there is no CPU path' % counts.device)
+    if counts.dtype != torch.int64 or not counts.is_contiguous() or tuple(counts.shape) != (A, 4) or counts.device != logits.device:
+        raise TypeError('sigmoid_xent_stats_update: counts must be a contiguous int64 [A, 4] tensor on the device of the logits (got %s %s on %s)'
+                        % (counts.dtype, tuple(counts.shape), counts.device))
+    if loss_sum.numel() != A or loss_sum.device != logits.device:
+        raise ValueError('sigmoid_xent_stats_update: loss_sum must be [A] on the device of the logits')
+    _abi.check(lib.igan_sigmoid_xent_stats_update(_stream(), _ptr(loss), _ptr(logits), _ptr(targets), _ptr(loss_sum), _ptr(counts), n, A))
+
+
+def binary_probs(logits):
+    """probs [A, n, 2] fp32 of logits [n, A] fp32 (igan_binary_probs): probs[a] is softmax(concat([x_a, -x_a], axis=1)), the
+    pair the reference's linear separability forms per attribute classifier (:138), for all attributes in one pass --
+    (1 / (1 + exp(-2x)), 1 / (1 + exp(2x))) in fp64, rounded once.  Attribute-major: probs[a] is contiguous."""
+    lib = _abi.get_plugin()
+    _require_rows_f32('binary_probs', logits)
+    n, A = (int(v) for v in logits.shape)
+    probs = torch.empty((A, n, 2), device=logits.device, dtype=torch.float32)
+    _abi.check(lib.igan_binary_probs(_stream(), _ptr(logits), _ptr(probs), n, A))
+    return probs
+
+
+class _SigmoidXentGradFn(torch.autograd.Function):
+    """The backward kernel as a node of its own, so that differentiating it again is an error and not a silent zero."""
+
+    @staticmethod
+    def forward(ctx, dloss, logits, targets, pos_weight):
+        return sigmoid_xent_bwd_raw(logits, targets, dloss, pos_weight)
+
+    @staticmethod
+    def backward(ctx, g):
+        raise NotImplementedError('sigmoid cross-entropy: second-order gradients are not built (the classifier loss is first-order)')
+
+
+class SigmoidXentFn(torch.autograd.Function):
+    """Per-element sigmoid cross-entropy of logits [n, A] fp32 against targets [n, A] fp32 in {0, 1} on the device, with an
+    optional pos_weight [A]: returns (loss [n, A] fp32, pred [n, A] int8); a target that is neither 0 nor 1 ignores its
+    element.  Only the logits are differentiated."""
+
+    @staticmethod
+    def forward(ctx, logits, targets, pos_weight=None):
+        logits = logits.contiguous()
+        loss, pred = sigmoid_xent_raw(logits, targets, pos_weight)
+        ctx.save_for_backward(logits, targets)
+        ctx.pos_weight = pos_weight
+        ctx.mark_non_differentiable(pred)
+        ctx.set_materialize_grads(False)        # no zero-filled int8 [n, A] gradient for pred on every backward
+        return loss, pred
+
+    @staticmethod
+    def backward(ctx, g, _g_pred):
+        if g is None:
+            return None, None, None
+        logits, targets = ctx.saved_tensors
+        if torch.is_grad_enabled():
+            return _SigmoidXentGradFn.apply(g, logits, targets, ctx.pos_weight), None, None
+        return sigmoid_xent_bwd_raw(logits, targets, g, ctx.pos_weight), None, None
+
+
+class BinaryXentStats:
+    """Per-attribute mean loss, accuracy and balanced accuracy of a stream of multi-label classifier steps, kept on the
+    device.  update(loss, logits, targets) folds a step's [n, A] elements (igan_sigmoid_xent_stats_update) and synchronises
+    nothing; to_host() is the one device -> host copy -> (mean loss [A], accuracy [A], balanced accuracy [A]) over the
+    elements that are not ignored (NaN where there is none; balanced accuracy is the mean of the recall of the positives and
+    of the negatives, and the recall of the class present when the other is absent); reset() starts the next tick."""
+
+    def __init__(self, A, device):
+        A = int(A)
+        if A < 1:
+            raise ValueError('BinaryXentStats: A must be positive (got %d)' % A)
+        self.A, self.device = A, torch.device(device)
+        self.loss_sum = torch.zeros(A, device=self.device, dtype=torch.float64)
+        self.counts = torch.zeros((A, 4), device=self.device, dtype=torch.int64)
+
+    def update(self, loss, logits, targets):
+        sigmoid_xent_stats_update_raw(loss.detach(), logits.detach().contiguous(), targets, self.loss_sum, self.counts)
+
+    def reset(self):
+        self.loss_sum.zero_()
+        self.counts.zero_()
+
+    def sums(self):
+        """(loss sums [A] float64, counts [A, 4] int64: tp, fp, tn, fn) on the host."""
+        both = torch.cat([self.loss_sum.unsqueeze(1), self.counts.to(torch.float64)], dim=1).cpu().numpy()     # counts < 2^53: exact
+        return both[:, 0].copy(), both[:, 1:].astype(np.int64)
+
+    def to_host(self):
+        return self.rates(*self.sums())
+
+    @staticmethod
+    def rates(loss_sum, counts):
+        """(mean loss [A], accuracy [A], balanced accuracy [A]) from what sums() returned."""
+        tp, fp, tn, fn = (counts[:, i].astype(np.float64) for i in range(4))
+        with np.errstate(divide='ignore', invalid='ignore'):
+            counted = tp + fp + tn + fn
+            recall_pos, recall_neg = tp / (tp + fn), tn / (tn + fp)
+            balanced = np.where(tp + fn == 0, recall_neg, np.where(tn + fp == 0, recall_pos, 0.5 * (recall_pos + recall_neg)))
+            return loss_sum / counted, (tp + tn) / counted, balanced
+
+
 def split_bounds(num_images, num_splits):
     """(begin, end) of every split of metrics/inception_score.py:50-51: split s holds rows s N // S .. (s + 1) N // S."""
     num_images, num_splits = int(num_images), int(num_splits)

@@ -18,15 +18,39 @@ together: gradient, Hessian-vector product and line search are one pass each ove
 
 The 40 CelebA-HQ attribute classifiers of the reference (celebahq-classifier-00-male.pkl .. -39-wearing-necktie.pkl) are
 not available; `LS` takes `classify_fns`: attribute index -> callable(float images [n, C, H, W] in G's range, box-mean
-downsampled to 256 when larger) -> logits [n, 1]."""
+downsampled to 256 when larger) -> logits [n, 1].  With none injected it loads this project's own attribute classifier from
+`classifier_pkl` (metrics/celeba_attribute_classifier.pkl, written by `python -m inclusivegan_amd.train_classifier --mode
+attributes`): one network with one output per CelebA attribute, so a minibatch costs ONE forward and one pass of
+hip_ops.binary_probs (csrc/sigmoid_xent.hip) instead of 40 forwards.  `ls` numbers obtained with that classifier are
+comparable between models evaluated with the same pickle; they are not comparable to numbers obtained with the reference's
+CelebA-HQ classifiers."""
 import collections
+import os
 
 import numpy as np
 import torch
 
 from .. import hip_ops
 from ..dnnlib.tflib import tfutil
+from ..training.imle import CELEBA_ATTRIBUTES
 from . import metric_base
+
+DEFAULT_CLASSIFIER_PKL = 'metrics/celeba_attribute_classifier.pkl'      # relative to the working directory, as the Stacked-MNIST pickle
+
+# The reference numbers its 40 classifiers in its own order (the file names in the comments of classifier_urls, :21-60): male,
+# smiling, attractive, wavy hair, young, then CelebA's remaining 35 attributes alphabetically.  attrib_idx indexes THIS list;
+# the column of a classifier trained on `dataset_tool.py create_celeba` labels is the name's place in imle.CELEBA_ATTRIBUTES.
+LS_ATTRIBUTE_NAMES = tuple(
+    'Male Smiling Attractive Wavy_Hair Young '
+    '5_o_Clock_Shadow Arched_Eyebrows Bags_Under_Eyes Bald Bangs Big_Lips Big_Nose Black_Hair Blond_Hair Blurry Brown_Hair '
+    'Bushy_Eyebrows Chubby Double_Chin Eyeglasses Goatee Gray_Hair Heavy_Makeup High_Cheekbones Mouth_Slightly_Open Mustache '
+    'Narrow_Eyes No_Beard Oval_Face Pale_Skin Pointy_Nose Receding_Hairline Rosy_Cheeks Sideburns Straight_Hair Wearing_Earrings '
+    'Wearing_Hat Wearing_Lipstick Wearing_Necklace Wearing_Necktie'.split())
+
+
+def attribute_column(attrib_idx):
+    """Column of imle.CELEBA_ATTRIBUTES that holds the attribute the reference numbers attrib_idx."""
+    return CELEBA_ATTRIBUTES.index(LS_ATTRIBUTE_NAMES[attrib_idx])
 
 # ---- information functions (:65-99), value for value: float32 normalisation, bits, the clamp at 0 ------------------------------
 
@@ -291,14 +315,15 @@ def confusion_table(svm_outputs, svm_targets):
 
 
 class LS(metric_base.MetricBase):
-    def __init__(self, num_samples, num_keep, attrib_indices, minibatch_per_gpu, classify_fns=None, **kwargs):
+    def __init__(self, num_samples, num_keep, attrib_indices, minibatch_per_gpu, classify_fns=None, classifier_pkl=DEFAULT_CLASSIFIER_PKL, **kwargs):
         assert num_keep <= num_samples
         super().__init__(**kwargs)
         self.num_samples = num_samples
         self.num_keep = num_keep
         self.attrib_indices = attrib_indices
         self.minibatch_per_gpu = minibatch_per_gpu
-        self.classify_fns = classify_fns
+        self.classify_fns = classify_fns        # injected functions always win; None: classifier_pkl is loaded when it exists
+        self.classifier_pkl = classifier_pkl
         self.results = None             # what the sampling loop collected: latents, dlatents, attribute index -> [n, 2]
         self.fits = None                # space -> SvcFit of the last run
 
@@ -315,6 +340,12 @@ class LS(metric_base.MetricBase):
                 images = images.reshape(-1, images.shape[1], images.shape[2] // factor, factor, images.shape[3] // factor, factor).mean(dim=(3, 5))
             chunks['latents'].append(latents.to(torch.float32))
             chunks['dlatents'].append(dlatents[:, -1].to(torch.float32))
+            if hasattr(self.classify_fns, 'classify_all'):      # one network, one output per attribute: one forward, one kernel
+                logits = torch.as_tensor(self.classify_fns.classify_all(images)).to(dev, torch.float32).contiguous()
+                probs = hip_ops.binary_probs(logits)            # [A, n, 2], attribute-major
+                for attrib_idx in self.attrib_indices:
+                    chunks[attrib_idx].append(probs[attribute_column(attrib_idx)])
+                continue
             for attrib_idx in self.attrib_indices:
                 logits = torch.as_tensor(self.classify_fns[attrib_idx](images)).to(dev, torch.float32).reshape(-1, 1)
                 chunks[attrib_idx].append(torch.softmax(torch.cat([logits, -logits], dim=1), dim=1))
@@ -322,6 +353,13 @@ class LS(metric_base.MetricBase):
 
     def _evaluate(self, Gs, Gs_kwargs, num_gpus):
         attribs = list(self.attrib_indices)
+        if self.classify_fns is None and self.classifier_pkl is not None and os.path.isfile(self.classifier_pkl):
+            from ..train_classifier import load_attribute_classifier
+            self.classify_fns = load_attribute_classifier(self.classifier_pkl, device=Gs.device)
+            missing = [a for a in attribs if a not in self.classify_fns]
+            if missing:
+                raise RuntimeError('LS: the classifier of %s has %d outputs and none for attribute indices %s'
+                                   % (self.classifier_pkl, self.classify_fns.num_attributes, missing))
         if self.classify_fns is None or any(a not in self.classify_fns for a in attribs):
             raise RuntimeError('LS needs classify_fns: the reference\'s celebahq-classifier-00-male.pkl .. '
                                'celebahq-classifier-39-wearing-necktie.pkl are not available in this tree')

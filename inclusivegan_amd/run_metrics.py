@@ -3,7 +3,8 @@
 
 The networks whose pickles are not available here (Inception features / softmax, the attribute classifiers) are injected:
 `inject` maps a constructor keyword (feature_fn, classify_fn, classify_fns) to a callable; on the command line
-`--inject KEY=dotted.name` names it."""
+`--inject KEY=dotted.name` names it.  Without one, mode_counts* / KL* and ls load the classifiers train_classifier.py wrote under
+metrics/ of the working directory (this project's own networks)."""
 import argparse
 import inspect
 import os
