@@ -44,7 +44,8 @@ extern "C" {
  * igan_images_to_uint8, igan_images_from_uint8, igan_dense_small2_grouped, igan_dense_small_wgrad2_grouped, igan_rows_group_sum,
  * igan_scale_add, igan_kmeans_workspace_bytes, igan_kmeans_step, igan_moments_workspace_bytes, igan_moments_update, igan_moments_finalize,
  * igan_moments_merge, igan_class_hist_update, igan_prob_stats_update, igan_nnk_update, igan_softmax_xent_fwd, igan_softmax_xent_bwd,
- * igan_xent_stats_update, igan_sigmoid_xent_fwd, igan_sigmoid_xent_bwd, igan_sigmoid_xent_stats_update, igan_binary_probs). */
+ * igan_xent_stats_update, igan_sigmoid_xent_fwd, igan_sigmoid_xent_bwd, igan_sigmoid_xent_stats_update, igan_binary_probs,
+ * igan_filter_images_grouped (with struct igan_filter_image_desc, igan_struct_size id 9), igan_debug_filter_image_launches). */
 #define IGAN_ABI_VERSION 10
 
 typedef void* igan_stream_t; /* hipStream_t */
@@ -58,7 +59,7 @@ enum igan_status {
 
 int igan_abi_version(void);
 /* sizeof() of the parameter structs as this library was compiled, by id: 0 upfirdn2d, 1 fused_bias_act, 2 conv2d,
- * 3 conv2d_wgrad, 4 dense, 5 dense_wgrad, 6 taps, 7 dense2, 8 dense_wgrad2; 0 for an unknown id.  A binding checks these against its own
+ * 3 conv2d_wgrad, 4 dense, 5 dense_wgrad, 6 taps, 7 dense2, 8 dense_wgrad2, 9 filter_image_desc; 0 for an unknown id.  A binding checks these against its own
  * struct declarations at load time, so that a stale library can never be driven with a newer struct (or vice versa). */
 size_t igan_struct_size(int which);
 const char* igan_last_error(void);
@@ -295,6 +296,17 @@ int igan_conv_piece_form(void);
  * the piece form).  igan_filter_image: writes it (16-byte aligned `out`; the same kernels igan_conv2d runs for its own image, so results are bit-identical). */
 size_t igan_filter_image_bytes(int KH, int KW, int Cin, int Cout);
 int igan_filter_image(igan_stream_t stream, const float* w, void* out, int KH, int KW, int Cin, int Cout, int w_transposed);
+/* Grouped form (fp16 form only; IGAN_ERR_UNSUPPORTED under the bf16-piece form and with the piece forms off): the images of `count` (<= IGAN_FILTER_MAX_GROUPS)
+ * filters in exactly TWO kernel launches, whatever `count` is -- the column maxima of all entries, then the images and 1 / S of all entries.  An entry is what one
+ * igan_filter_image call takes, and its image is byte for byte what that call writes, so a convolution call may be handed it as w_pieces.  For weights that change
+ * between the ops of a training loop but not inside one: every filter image an op needs, written at its top from the current weights.  Checked before any device
+ * work (igan_last_error() names the entry): every entry has igan_filter_image_bytes() != 0, 16-byte aligned w / out, and no two `out` ranges overlap. */
+#define IGAN_FILTER_MAX_GROUPS 48
+typedef struct igan_filter_image_desc { const float* w; void* out; int KH, KW, Cin, Cout, w_transposed; } igan_filter_image_desc;
+int igan_filter_images_grouped(igan_stream_t stream, const igan_filter_image_desc* groups, int count);
+/* Diagnostic (host side, no device work): kernel launches issued for filter images so far -- by igan_conv2d for its own image, igan_filter_image and
+ * igan_filter_images_grouped; reset != 0 zeroes the counter after reading it. */
+int igan_debug_filter_image_launches(unsigned long long* out, int reset);
 /* ABI v8: size in floats of an x_colmax / dy_colmax buffer for a tensor [N, HW, C]; 0 = none is taken (not the fp16 form, a channel count outside it, or fewer
  * pixels than any weight gradient that takes the column image has: N * HW below the piece form's row threshold). */
 size_t igan_colmax_floats(int N, int HW, int C);

@@ -132,11 +132,17 @@ class DenseWgrad2Params(ctypes.Structure):
     ]
 
 
+class FilterImageDesc(ctypes.Structure):
+    _fields_ = [('w', ctypes.c_void_p), ('out', ctypes.c_void_p),
+                ('KH', ctypes.c_int), ('KW', ctypes.c_int), ('Cin', ctypes.c_int), ('Cout', ctypes.c_int), ('w_transposed', ctypes.c_int)]
+
+
 ABI_VERSION = 10     # include/igan_hip.h IGAN_ABI_VERSION
 STRUCTS = (UpFirDn2DParams, FusedBiasActParams, Conv2DParams, Conv2DWgradParams, DenseParams, DenseWgradParams, TapsParams,
-           Dense2Params, DenseWgrad2Params)   # igan_struct_size ids
+           Dense2Params, DenseWgrad2Params, FilterImageDesc)   # igan_struct_size ids
 
 DENSE_MAX_GROUPS = 24
+FILTER_MAX_GROUPS = 48      # IGAN_FILTER_MAX_GROUPS
 DENSE_PRO_NONE, DENSE_PRO_SQUARE, DENSE_PRO_DEMOD_GRAD = 0, 1, 2
 DENSE_EPI_SCALE, DENSE_EPI_BIAS, DENSE_EPI_RSQRT, DENSE_EPI_STYLE_GRAD = 0, 1, 2, 3
 DENSE_PRO_MUL = 3                                                      # second-order style path (igan_dense_small2_grouped)
@@ -171,6 +177,8 @@ SIGNATURES = {
     'igan_colmax_floats': (ctypes.c_size_t, [_I, _I, _I]),
     'igan_filter_image_bytes': (ctypes.c_size_t, [_I, _I, _I, _I]),
     'igan_filter_image': (_I, [_P, _P, _P, _I, _I, _I, _I, _I]),
+    'igan_filter_images_grouped': (_I, [_P, ctypes.POINTER(FilterImageDesc), _I]),
+    'igan_debug_filter_image_launches': (_I, [_P, _I]),
     'igan_to_pieces': (_I, [_P, _P, _P, _P, _I, _I, _I]),
     'igan_conv_pieces_wanted': (_I, [_I, _I, _I, _I]),
     'igan_pieces_image_ok': (_I, [_I, _I, _I]),

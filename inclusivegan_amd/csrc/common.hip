@@ -31,6 +31,7 @@ extern "C" size_t igan_struct_size(int which) {
         case 6: return sizeof(igan_taps_params);
         case 7: return sizeof(igan_dense2_params);
         case 8: return sizeof(igan_dense_wgrad2_params);
+        case 9: return sizeof(igan_filter_image_desc);
         default: return 0;
     }
 }

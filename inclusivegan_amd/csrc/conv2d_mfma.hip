@@ -45,6 +45,7 @@
 //    kernel adds them in fixed order (bit-reproducible, no float atomics) -- the fix-up traffic is that
 //    of the tail tiles only, not of the whole output.
 #include "igan_common.h"
+#include <atomic>
 #include <cmath>
 #include <cstdlib>
 #include <type_traits>
@@ -1362,10 +1363,11 @@ __global__ __launch_bounds__(256) void cols_f16_kernel(const float* __restrict__
 // Column maxima of a filter: the largest |W(tap, k, n)| over k per (tap [, k quarter], n).  The image kernel below takes the maximum over the partial rows.
 //   !WT: w[tap][k][n] (HWIO; n contiguous): grid (taps * H_KSK, ceil(Nn / 64)), 4 row lanes x 64 columns, partial[(tap * H_KSK + j) * Nn + n]
 //    WT: w[tap][n][k] (k contiguous): one wave per (tap, n) row, partial[tap * Nn + n]
+// (the body: `bx`, `by` are the block's place in the grid described above -- blockIdx of filter_amax_kernel, an entry's share of filter_amax_grouped_kernel)
 template <bool WT>
-__global__ __launch_bounds__(256) void filter_amax_kernel(const float* __restrict__ w, float* __restrict__ partial, int taps, int Nn, int K) {
+__device__ __forceinline__ void filter_amax_body(const float* __restrict__ w, float* __restrict__ partial, int taps, int Nn, int K, unsigned bx, unsigned by) {
     if constexpr (WT) {
-        const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+        const int row = bx * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
         if (row >= taps * Nn) return;
         const float4* src = reinterpret_cast<const float4*>(w + (size_t)row * K);
         float m = 0.0f;
@@ -1375,8 +1377,8 @@ __global__ __launch_bounds__(256) void filter_amax_kernel(const float* __restric
         if (lane == 0) partial[row] = m;
     } else {
         __shared__ float red[256];
-        const int tap = blockIdx.x / H_KSK, j = blockIdx.x - tap * H_KSK;
-        const int n = blockIdx.y * 64 + (threadIdx.x & 63), rl = threadIdx.x >> 6;
+        const int tap = bx / H_KSK, j = bx - tap * H_KSK;
+        const int n = by * 64 + (threadIdx.x & 63), rl = threadIdx.x >> 6;
         const int k0 = (int)(((long long)j * K) / H_KSK), k1 = (int)(((long long)(j + 1) * K) / H_KSK);
         float m = 0.0f;
         if (n < Nn) {
@@ -1392,17 +1394,21 @@ __global__ __launch_bounds__(256) void filter_amax_kernel(const float* __restric
         }
         red[threadIdx.x] = m;
         __syncthreads();
-        if (rl == 0 && n < Nn) partial[(size_t)blockIdx.x * Nn + n] = fmaxf(fmaxf(m, red[64 + threadIdx.x]), fmaxf(red[128 + threadIdx.x], red[192 + threadIdx.x]));
+        if (rl == 0 && n < Nn) partial[(size_t)bx * Nn + n] = fmaxf(fmaxf(m, red[64 + threadIdx.x]), fmaxf(red[128 + threadIdx.x], red[192 + threadIdx.x]));
     }
+}
+template <bool WT>
+__global__ __launch_bounds__(256) void filter_amax_kernel(const float* __restrict__ w, float* __restrict__ partial, int taps, int Nn, int K) {
+    filter_amax_body<WT>(w, partial, taps, Nn, K, blockIdx.x, blockIdx.y);
 }
 
 // filter -> [K/16][tap][n][2][16] fp16 with one scale per OUTPUT channel n (orientation as filter_planes_kernel); 1 / S_n to inv[Nn].
 // partial: `prow` rows of Nn column maxima (filter_amax_kernel).
 template <bool WT>
-__global__ __launch_bounds__(256) void filter_planes_f16_kernel(const float* __restrict__ w, unsigned short* __restrict__ out, float* __restrict__ inv,
-                                                                 const float* __restrict__ partial, int prow, int taps, int KW_, int Nn, int K) {
+__device__ __forceinline__ void filter_planes_f16_body(const float* __restrict__ w, unsigned short* __restrict__ out, float* __restrict__ inv,
+                                                       const float* __restrict__ partial, int prow, int taps, int Nn, int K, unsigned bx) {
     const int cpk = K >> 4;
-    const int idx = blockIdx.x * 256 + threadIdx.x;
+    const int idx = bx * 256 + threadIdx.x;
     if (idx >= taps * Nn * cpk) return;
     int tap, n, c;
     if constexpr (WT) { c = idx % cpk; const int r = idx / cpk; n = r % Nn; tap = r / Nn; }
@@ -1447,6 +1453,48 @@ __global__ __launch_bounds__(256) void filter_planes_f16_kernel(const float* __r
             u.z = pc[q][8 * hh + 4] | ((unsigned)pc[q][8 * hh + 5] << 16); u.w = pc[q][8 * hh + 6] | ((unsigned)pc[q][8 * hh + 7] << 16);
             dst[2 * q + hh] = u;
         }
+}
+template <bool WT>
+__global__ __launch_bounds__(256) void filter_planes_f16_kernel(const float* __restrict__ w, unsigned short* __restrict__ out, float* __restrict__ inv,
+                                                                 const float* __restrict__ partial, int prow, int taps, int KW_, int Nn, int K) {
+    filter_planes_f16_body<WT>(w, out, inv, partial, prow, taps, Nn, K, blockIdx.x);
+}
+
+// Grouped form (igan_filter_images_grouped): the filter images of up to IGAN_FILTER_MAX_GROUPS filters in TWO launches -- the column maxima of all of them, then
+// the images and 1 / S of all of them -- with the bodies above, so an entry's bytes are those of its own igan_filter_image call.  The table travels by value (the
+// kernarg segment); aend / pend are the running block counts of the two launches, and a block finds its entry by a bisection on them that is the same for the
+// whole workgroup (blockIdx only: scalar loads).
+struct FilterGroups {
+    struct Entry { const float* w; unsigned short* out; int taps, Nn, K, wt; } g[IGAN_FILTER_MAX_GROUPS];
+    int aend[IGAN_FILTER_MAX_GROUPS], pend[IGAN_FILTER_MAX_GROUPS];
+    int count;
+};
+__device__ __forceinline__ int filter_group_of(const int (&end)[IGAN_FILTER_MAX_GROUPS], int count, int b) {
+    int lo = 0, hi = count - 1;         // the first entry whose running count exceeds b (b < end[count - 1]: the grid)
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (b >= end[mid]) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+__global__ __launch_bounds__(256) void filter_amax_grouped_kernel(FilterGroups G) {
+    const int e = filter_group_of(G.aend, G.count, (int)blockIdx.x);
+    const unsigned b = blockIdx.x - (unsigned)(e > 0 ? G.aend[e - 1] : 0);
+    const float* __restrict__ w = G.g[e].w;
+    const int taps = G.g[e].taps, Nn = G.g[e].Nn, K = G.g[e].K;
+    float* partial = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(G.g[e].out) + (size_t)taps * Nn * K * 4) + Nn;
+    if (G.g[e].wt) filter_amax_body<true>(w, partial, taps, Nn, K, b, 0);
+    else { const unsigned gx = (unsigned)(taps * H_KSK); filter_amax_body<false>(w, partial, taps, Nn, K, b % gx, b / gx); }
+}
+__global__ __launch_bounds__(256) void filter_planes_f16_grouped_kernel(FilterGroups G) {
+    const int e = filter_group_of(G.pend, G.count, (int)blockIdx.x);
+    const unsigned b = blockIdx.x - (unsigned)(e > 0 ? G.pend[e - 1] : 0);
+    const float* __restrict__ w = G.g[e].w;
+    unsigned short* __restrict__ out = G.g[e].out;
+    const int taps = G.g[e].taps, Nn = G.g[e].Nn, K = G.g[e].K;
+    float* inv = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(out) + (size_t)taps * Nn * K * 4);
+    if (G.g[e].wt) filter_planes_f16_body<true>(w, out, inv, inv + Nn, taps, taps, Nn, K, b);
+    else filter_planes_f16_body<false>(w, out, inv, inv + Nn, taps * H_KSK, taps, Nn, K, b);
 }
 
 // TAPO (the fp16 form, NP == 2): the reduction runs TAP outermost, the 16-channel slices of a tap inside it.  A row's pixel -- and with it the row's scale --
@@ -2986,8 +3034,11 @@ void launch_col_image(hipStream_t stream, const float* x, const float* scale, un
 // A/B switch inside the fp16 form's forward / data-gradient tile: IGAN_F16_W4=0 takes the eight-wave tile (conv_fwd_planes_kernel<2, true>: same products and
 // folds per output element, the bit-for-bit witness of the four-wave tile in tests/test_gpu_planes_variant.py)
 bool f16_w4() { static const int v = getenv("IGAN_F16_W4") ? atoi(getenv("IGAN_F16_W4")) : 1; return v != 0; }
+// Diagnostic (igan_debug_filter_image_launches): filter-image kernel launches issued so far, single and grouped paths alike (host side, counted where issued)
+std::atomic<unsigned long long> g_filter_image_launches{0ull};
 void launch_filter_image(hipStream_t stream, const float* w, unsigned short* wp, bool wt, int taps, int KW_, int Nn, int K) {
     const int wtotal = taps * Nn * (K / PK);
+    g_filter_image_launches += planes_mode() == 2 ? 2ull : 1ull;
     if (planes_mode() == 2) {
         float* inv = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(wp) + (size_t)taps * Nn * K * 4);
         float* partial = inv + Nn;
@@ -3627,6 +3678,53 @@ extern "C" int igan_filter_image(igan_stream_t stream_, const float* w, void* ou
     IGAN_REQUIRE(((((uintptr_t)w) | ((uintptr_t)out)) & 15) == 0, "filter_image: w and out must be 16-byte aligned");
     launch_filter_image((hipStream_t)stream_, w, reinterpret_cast<unsigned short*>(out), w_transposed != 0, KH * KW, KW, Cout, Cin);
     IGAN_LAUNCH_CHECK("filter_image launch");
+    return IGAN_OK;
+}
+
+// Grouped form: the images of `count` filters in two launches (filter_amax_grouped_kernel, filter_planes_f16_grouped_kernel).  Everything is checked before
+// anything is launched; an entry's bytes are those its own igan_filter_image call writes (same bodies; a maximum is exact and order-free, the split element-wise).
+extern "C" int igan_filter_images_grouped(igan_stream_t stream_, const igan_filter_image_desc* groups, int count) {
+    using namespace igan;
+    IGAN_REQUIRE(groups != nullptr && count >= 1 && count <= IGAN_FILTER_MAX_GROUPS, "filter_images_grouped: 1 <= count <= %d entries", IGAN_FILTER_MAX_GROUPS);
+    if (planes_mode() != 2) return igan::fail(IGAN_ERR_UNSUPPORTED, "filter_images_grouped: only the two-piece fp16 form (igan_conv_piece_form() == 2) has a grouped filter image");
+    FilterGroups G;
+    size_t bytes[IGAN_FILTER_MAX_GROUPS];
+    long long ablocks = 0, pblocks = 0;
+    for (int i = 0; i < count; i++) {
+        const igan_filter_image_desc& d = groups[i];
+        IGAN_REQUIRE(d.w != nullptr && d.out != nullptr, "filter_images_grouped: entry %d: null buffer", i);
+        bytes[i] = igan_filter_image_bytes(d.KH, d.KW, d.Cin, d.Cout);
+        IGAN_REQUIRE(bytes[i] != 0, "filter_images_grouped: entry %d: igan_filter_image_bytes() says this process / filter (%dx%d, Cin %d, Cout %d) takes none", i, d.KH, d.KW, d.Cin, d.Cout);
+        IGAN_REQUIRE(((((uintptr_t)d.w) | ((uintptr_t)d.out)) & 15) == 0, "filter_images_grouped: entry %d: w and out must be 16-byte aligned", i);
+        for (int j = 0; j < i; j++) {
+            const uintptr_t a0 = (uintptr_t)groups[j].out, b0 = (uintptr_t)d.out;
+            IGAN_REQUIRE(a0 + bytes[j] <= b0 || b0 + bytes[i] <= a0, "filter_images_grouped: entry %d: its image overlaps entry %d's", i, j);
+        }
+        const int taps = d.KH * d.KW, Nn = d.Cout, K = d.Cin;
+        const bool wt = d.w_transposed != 0;
+        G.g[i].w = d.w; G.g[i].out = reinterpret_cast<unsigned short*>(d.out);
+        G.g[i].taps = taps; G.g[i].Nn = Nn; G.g[i].K = K; G.g[i].wt = wt ? 1 : 0;
+        ablocks += wt ? ceil_div(taps * Nn, 4) : taps * H_KSK * ceil_div(Nn, 64);      // the grids of launch_filter_image
+        pblocks += ceil_div(taps * Nn * (K / PK), 256);
+        G.aend[i] = (int)ablocks; G.pend[i] = (int)pblocks;
+    }
+    for (int i = count; i < IGAN_FILTER_MAX_GROUPS; i++) {
+        G.g[i].w = nullptr; G.g[i].out = nullptr; G.g[i].taps = G.g[i].Nn = G.g[i].K = G.g[i].wt = 0;
+        G.aend[i] = (int)ablocks; G.pend[i] = (int)pblocks;
+    }
+    G.count = count;
+    g_filter_image_launches += 2ull;
+    hipLaunchKernelGGL(filter_amax_grouped_kernel, dim3((unsigned)ablocks), dim3(256), 0, (hipStream_t)stream_, G);
+    hipLaunchKernelGGL(filter_planes_f16_grouped_kernel, dim3((unsigned)pblocks), dim3(256), 0, (hipStream_t)stream_, G);
+    IGAN_LAUNCH_CHECK("filter_images_grouped launch");
+    return IGAN_OK;
+}
+
+// Diagnostic: kernel launches issued for filter images so far (igan_conv2d's own, igan_filter_image, igan_filter_images_grouped); host-side, no device work.
+extern "C" int igan_debug_filter_image_launches(unsigned long long* out, int reset) {
+    using namespace igan;
+    IGAN_REQUIRE(out != nullptr, "debug_filter_image_launches: null argument");
+    *out = reset ? g_filter_image_launches.exchange(0ull) : g_filter_image_launches.load();
     return IGAN_OK;
 }
 

@@ -126,8 +126,17 @@ class GraphedStep:
         self.out = None
         self.captured_generation = 0
         self.replays = 0        # replays of the CURRENT graph (first capture counts: a capture does not execute, the replay after it does)
+        self.filter_scope = None    # hip_ops.FilterImageScope: the op's filter images, written at the top of each execution (made at the first one)
 
     def _run_fn(self):
+        # every execution of the op -- eager, capture, the eager side of check_replay -- runs inside the op's filter image scope: the first one records which
+        # filters the library images, the later ones write them all up front in two launches (IGAN_FILTER_GROUP=0: off)
+        from ... import hip_ops
+        if self.filter_scope is None:
+            self.filter_scope = hip_ops.FilterImageScope(self.name)
+        return self.filter_scope.run(self._run_fn_unscoped)
+
+    def _run_fn_unscoped(self):
         # a TapRandom source groups the draws by op: tell it which op's Python is about to run (eager call or capture)
         src = tfutil.random_source()
         if hasattr(src, 'begin'):
@@ -238,6 +247,8 @@ class GraphedStep:
             self.out = None
         if self.graph is None:
             torch.cuda.synchronize()
+            if self.filter_scope is not None:
+                self.filter_scope.prepare()         # its arena is persistent: allocated here, outside the capture
             g = torch.cuda.CUDAGraph()
             # With a process group up, RCCL's watchdog thread polls events while we capture: in the default
             # "global" mode that foreign call would invalidate the capture; only this thread's calls matter here.

@@ -676,6 +676,135 @@ def _constant_filter_image(lib, w, geom, cin, cout, w_transposed):
     return PieceImage(img, nbytes)
 
 
+FILTER_GROUP = os.environ.get('IGAN_FILTER_GROUP', '1') != '0'      # A/B switch: 0 = no per-op filter image scope, every call images its filter itself
+_filter_scope = None        # the FilterImageScope of the training op that is executing (None outside one: nothing changes for any other caller)
+
+
+def filter_image_launches(reset=False):
+    """Diagnostic: filter-image kernel launches the library has issued so far (its own per call, igan_filter_image, the grouped form)."""
+    n = ctypes.c_ulonglong(0)
+    _abi.check(_abi.get_plugin().igan_debug_filter_image_launches(ctypes.byref(n), 1 if reset else 0))
+    return int(n.value)
+
+
+class FilterImageScope:
+    """The filter images of ONE training op, written at the top of every execution of it (fp16 form; include/igan_hip.h igan_filter_images_grouped).
+
+    A filter image depends on the weights and the orientation only, and no weight changes inside an op (the optimizer and the moving average run between
+    ops).  So `run(fn)` -- the op's every execution, eager, captured or the eager side of check_replay --
+      1st execution   records every (weight address, KH, KW, call Cin, call Cout, orientation) for which the LIBRARY wrote a filter image (conv2d_raw asks
+                      it: the call's kernel is a piece-form one and no constant image was handed over; no threshold is restated here);
+      before the 2nd  (`prepare()`, outside any stream capture) one persistent arena with a slice per recorded entry, the descriptor lists built once.  The
+                      recorded weight tensors are kept alive: views into the networks' flat buckets, whose addresses cannot then be handed to anything else;
+      from then on    the grouped call(s) first -- two launches per <= FILTER_MAX_GROUPS entries -- and every convolution call whose key is in the recorded
+                      set is handed its slice as w_pieces.  A call whose key is not (another address: a re-allocated network) images itself as before.
+    Nothing written here outlives the op's execution in meaning: the next execution rewrites every slice from the weights of that moment, so kernels that
+    write the buckets without touching a tensor's version counter (adam_step_raw, ema_raw) are seen.  mark_constant's cache is not involved."""
+
+    def __init__(self, name='op'):
+        self.name = name
+        self.state = 'new'          # 'new' -> 'recorded' -> 'ready' | 'off'
+        self.recorded = {}          # key -> (weight tensor, image bytes), in order of first use
+        self.slices = {}            # key -> PieceImage into the arena
+        self.arena = None
+        self.batches = []           # (ctypes array of FilterImageDesc, count)
+        self.hits = None            # keys consumed by the first prepared execution outside a capture (entries nobody consumes are dropped after it)
+
+    @staticmethod
+    def usable():
+        return FILTER_GROUP and _abi.get_plugin().igan_conv_piece_form() == 2
+
+    def note(self, lib, p, w, geom, cin, cout, w_transposed):
+        """Recording pass: did the library write a filter image for this call?"""
+        key = (w.data_ptr(), geom.kh, geom.kw, int(cin), int(cout), bool(w_transposed))
+        if key in self.recorded or (w.data_ptr() & 15):
+            return
+        buf = ctypes.create_string_buffer(128)
+        _abi.check(lib.igan_conv2d_kernel_name(ctypes.byref(p), buf, 128))
+        if not buf.value.decode().startswith('conv_fwd_planes'):
+            return
+        nbytes = int(lib.igan_filter_image_bytes(geom.kh, geom.kw, int(cin), int(cout)))
+        if nbytes:
+            self.recorded[key] = (w, nbytes)
+
+    def lookup(self, w, geom, cin, cout, w_transposed):
+        key = (w.data_ptr(), geom.kh, geom.kw, int(cin), int(cout), bool(w_transposed))
+        img = self.slices.get(key)
+        if img is not None and isinstance(self.hits, set):
+            self.hits.add(key)
+        return img
+
+    def _build(self, keys):
+        self.batches = []
+        for i in range(0, len(keys), _abi.FILTER_MAX_GROUPS):
+            part = keys[i:i + _abi.FILTER_MAX_GROUPS]
+            arr = (_abi.FilterImageDesc * len(part))()
+            for d, key in zip(arr, part):
+                d.w, d.out = key[0], self.slices[key].data_ptr()
+                d.KH, d.KW, d.Cin, d.Cout, d.w_transposed = key[1], key[2], key[3], key[4], 1 if key[5] else 0
+            self.batches.append((arr, len(part)))
+
+    def prepare(self):
+        """Allocate the arena and build the descriptors (once; not inside a stream capture, whose allocations belong to the graph's pool)."""
+        if self.state != 'recorded' or torch.cuda.is_current_stream_capturing():
+            return
+        if not self.recorded:
+            self.state = 'off'
+            return
+        offsets, total = {}, 0
+        for key, (w, nbytes) in self.recorded.items():
+            offsets[key] = total
+            total += (nbytes + 255) // 256 * 256
+        dev = next(iter(self.recorded.values()))[0].device
+        self.arena = torch.empty((total,), device=dev, dtype=torch.uint8)
+        if self.arena.data_ptr() & 255:
+            self.state = 'off'
+            return
+        self.slices = {key: PieceImage(self.arena[off:off + self.recorded[key][1]], self.recorded[key][1]) for key, off in offsets.items()}
+        self._build(list(self.recorded))
+        self.state = 'ready'
+
+    def _image(self):
+        lib = _abi.get_plugin()
+        def launch():
+            for arr, count in self.batches:
+                _abi.check(lib.igan_filter_images_grouped(_stream(), arr, count))
+        if stamp_log is not None:       # the conv family's time keeps the images it no longer sees in front of each call (no FLOPs of their own)
+            stamp_log.bracket('filter_images_grouped', 0.0, launch, shape='%-12s %d filters (%s)' % ('filters', len(self.slices), self.name))
+        else:
+            launch()
+
+    def run(self, fn):
+        global _filter_scope
+        if self.state == 'off' or not self.usable():
+            return fn()
+        self.prepare()
+        if self.state == 'recorded':        # recorded, but no chance yet to allocate outside a capture: per-call imaging
+            return fn()
+        outer = _filter_scope
+        first_ready = self.state == 'ready' and self.hits is None and not torch.cuda.is_current_stream_capturing()
+        if first_ready:
+            self.hits = set()
+        _filter_scope = self
+        try:
+            if self.state == 'ready':
+                self._image()
+            out = fn()
+        finally:
+            _filter_scope = outer
+        if self.state == 'new':
+            self.state = 'recorded'
+        elif first_ready:                   # an entry no call consumed (a weight that was a temporary of the recording pass) is not imaged again
+            used = [k for k in self.slices if k in self.hits]
+            self.hits = False
+            if len(used) != len(self.slices):
+                self.slices = {k: self.slices[k] for k in used}
+                self._build(used)
+                if not used:
+                    self.state = 'off'
+        return out
+
+
 def conv2d_raw(x, w, geom, out_hw, cout, w_transposed=False, in_scale=None, out_scale=None, bias=None, act=None, noise=None, strength=None, x_pieces=None, colmax=None):
     """x: logical [N,Cin,H,W] (channels_last).  w: HWIO [KH,KW,Cin,Cout] (or the forward layer's
     [KH,KW,Cout,Cin] when w_transposed).  Returns logical [N,Cout,OH,OW] channels_last.
@@ -685,6 +814,7 @@ def conv2d_raw(x, w, geom, out_hw, cout, w_transposed=False, in_scale=None, out_
     lib = _abi.get_plugin()
     _require_cuda_f32(x, w, in_scale, out_scale, bias)
     x = nhwc(x)
+    w_given = w
     w = w.contiguous()
     n, cin, h, wd = x.shape
     oh, ow = out_hw
@@ -715,6 +845,12 @@ def conv2d_raw(x, w, geom, out_hw, cout, w_transposed=False, in_scale=None, out_
     if wimg is not None:        # a constant filter's image, written once (mark_constant)
         p.w_pieces = wimg.data_ptr()
         p.w_pieces_bytes = wimg.nbytes
+    scope = _filter_scope if (wimg is None and w is w_given) else None      # a training op's filter image scope (a contiguous COPY of the weights has no address to go by)
+    if scope is not None and scope.state == 'ready':
+        wimg = scope.lookup(w, geom, cin, cout, w_transposed)
+        if wimg is not None:    # written at the top of this execution of the op from the weights as they are now
+            p.w_pieces = wimg.data_ptr()
+            p.w_pieces_bytes = wimg.nbytes
     if noise is not None:       # epilogue noise: [N or 1, 1, OH, OW] contiguous + device scalar strength (needs act)
         noise = noise.contiguous()
         _require_cuda_f32(noise, strength)
@@ -738,6 +874,8 @@ def conv2d_raw(x, w, geom, out_hw, cout, w_transposed=False, in_scale=None, out_
     if plan[0] > 1:
         p.splits = plan[0]
         p.sliced_tiles = plan[2]
+    if scope is not None and scope.state == 'new':
+        scope.note(lib, p, w, geom, cin, cout, w_transposed)
     if stamp_log is not None:
         buf = ctypes.create_string_buffer(128)
         _abi.check(lib.igan_conv2d_kernel_name(ctypes.byref(p), buf, 128))
