@@ -45,7 +45,8 @@ extern "C" {
  * igan_scale_add, igan_kmeans_workspace_bytes, igan_kmeans_step, igan_moments_workspace_bytes, igan_moments_update, igan_moments_finalize,
  * igan_moments_merge, igan_class_hist_update, igan_prob_stats_update, igan_nnk_update, igan_softmax_xent_fwd, igan_softmax_xent_bwd,
  * igan_xent_stats_update, igan_sigmoid_xent_fwd, igan_sigmoid_xent_bwd, igan_sigmoid_xent_stats_update, igan_binary_probs,
- * igan_filter_images_grouped (with struct igan_filter_image_desc, igan_struct_size id 9), igan_debug_filter_image_launches). */
+ * igan_filter_images_grouped (with struct igan_filter_image_desc, igan_struct_size id 9), igan_debug_filter_image_launches,
+ * igan_manifold_member_nn1_update). */
 #define IGAN_ABI_VERSION 10
 
 typedef void* igan_stream_t; /* hipStream_t */
@@ -567,6 +568,23 @@ int igan_manifold_member_update(igan_stream_t stream, const float* query, const 
                                 int* member /* [nq][nk], caller-initialised to 0 */,
                                 float* dots /* caller workspace, nq*nc floats */,
                                 int nq, int nc, int dim, int nk);
+
+/* igan_manifold_member_nn1_update: membership AND nearest neighbour of one candidate batch on ONE product block.  Its effect
+ * on member, best_d2 and best_idx is, bit for bit, that of igan_manifold_member_update followed by igan_nn1_update on the
+ * same arguments, with the product formed once (the precision pass of pr50k3 with realism / nearest index asks for both).
+ * Each half keeps its own rules: a query marked in every column skips the membership walk but not the nearest-neighbour
+ * one; the 1-NN drops a candidate its interval cannot decide, the membership test measures it.  The checks are those of the
+ * two entries: non-null buffers, the operand limits of igan_conv2d, 1 <= nk <= 8, idx_base >= 0 and idx_base + nc <=
+ * INT32_MAX (IGAN_ERR_INVALID_ARGUMENT), made before anything touches a device.
+ */
+int igan_manifold_member_nn1_update(igan_stream_t stream, const float* query, const float* qnorm,
+                                    const float* cand, const float* cnorm,
+                                    const double* cand_radius /* [nc][nk] */,
+                                    int* member /* [nq][nk], caller-initialised to 0 */,
+                                    double* best_d2 /* [nq], caller-initialised to +inf */,
+                                    int* best_idx /* [nq], caller-initialised to INT32_MAX */,
+                                    float* dots /* caller workspace, nq*nc floats */,
+                                    int nq, int nc, int dim, int nk, int idx_base);
 
 /* ------------------------------------------------------------------------
  * One exact k-means step for the PRD metric (reference: precision-recall-distributions/prd_score.py:125-127, the

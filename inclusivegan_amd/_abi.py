@@ -213,6 +213,7 @@ SIGNATURES = {
     'igan_nnk_update': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I]),
     'igan_knn_radius_update': (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I]),
     'igan_manifold_member_update': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I]),
+    'igan_manifold_member_nn1_update': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I]),
     'igan_kmeans_workspace_bytes': (_SZ, [_I, _I, _I]),
     'igan_kmeans_step': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I]),
     'igan_moments_workspace_bytes': (_SZ, [_I, _I]),

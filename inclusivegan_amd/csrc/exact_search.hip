@@ -350,3 +350,26 @@ extern "C" int igan_manifold_member_update(igan_stream_t stream_, const float* q
     IGAN_LAUNCH_CHECK("manifold_member_fold launch");
     return IGAN_OK;
 }
+
+// Membership and nearest neighbour of one candidate batch on ONE product block: distance_products() once, then the two fold
+// kernels above, unchanged, on the same `dots`.  Each fold keeps its own early exit and its own NaN policy, so member, best_d2
+// and best_idx are those of igan_manifold_member_update followed by igan_nn1_update by construction; the folds only read
+// `dots`, and the stream orders them after the product.
+extern "C" int igan_manifold_member_nn1_update(igan_stream_t stream_, const float* query, const float* qnorm,
+                                               const float* cand, const float* cnorm, const double* cand_radius,
+                                               int* member, double* best_d2, int* best_idx, float* dots,
+                                               int nq, int nc, int dim, int nk, int idx_base) {
+    IGAN_REQUIRE(query && qnorm && cand && cnorm && cand_radius && member && best_d2 && best_idx && dots,
+                 "manifold_member_nn1_update: null buffer");
+    if (int rc = check_batch("manifold_member_nn1_update", nq, nc, dim)) return rc;
+    IGAN_REQUIRE(nk >= 1 && nk <= 8, "manifold_member_nn1_update: nk must be in [1, 8]");
+    IGAN_REQUIRE(idx_base >= 0 && (long long)idx_base + nc <= INT32_MAX, "manifold_member_nn1_update: candidate index overflows int32");
+    if (int rc = distance_products(stream_, query, cand, dots, nq, nc, dim)) return rc;
+    hipLaunchKernelGGL(manifold_member_fold_kernel, dim3(ceil_div(nq, 4)), dim3(256), 0, (hipStream_t)stream_, dots, qnorm, cnorm,
+                       query, cand, cand_radius, member, nq, nc, dim, nk);
+    IGAN_LAUNCH_CHECK("manifold_member_fold launch");
+    hipLaunchKernelGGL(nn1_fold_kernel, dim3(ceil_div(nq, 4)), dim3(256), 0, (hipStream_t)stream_, dots, qnorm, cnorm, query, cand,
+                       best_d2, best_idx, nq, nc, dim, idx_base);
+    IGAN_LAUNCH_CHECK("nn1_fold launch");
+    return IGAN_OK;
+}

@@ -2398,6 +2398,25 @@ def manifold_member_update_raw(query, qnorm, cand, cnorm, cand_radius, member):
                                                _ptr(member), _ptr(dots), nq, nc, dim, nk))
 
 
+def manifold_member_nn1_update_raw(query, qnorm, cand, cnorm, cand_radius, member, best_d2, best_idx, idx_base):
+    """manifold_member_update_raw and nn1_update_raw of one candidate batch on ONE product block (igan_manifold_member_nn1_update):
+    member, best_d2 and best_idx end with the bits the two calls in that order leave."""
+    lib = _abi.get_plugin()
+    name = 'manifold_member_nn1_update'
+    query, qnorm, cand, cnorm, dots = _search_operands(name, query, qnorm, cand, cnorm)
+    (nq, dim), nc = query.shape, cand.shape[0]
+    if cand_radius.dtype != torch.float64 or cand_radius.dim() != 2 or not cand_radius.is_cuda:
+        raise TypeError('%s: cand_radius must be a device float64 [nc, nk]' % name)
+    _search_state(name, 'member', member, torch.int32, nq)
+    _search_state(name, 'best_d2', best_d2, torch.float64, nq, 1)
+    _search_state(name, 'best_idx', best_idx, torch.int32, nq, 1)
+    cand_radius, nk = cand_radius.contiguous(), member.shape[1]
+    if tuple(cand_radius.shape) != (nc, nk):
+        raise ValueError('%s: shapes of cand, cand_radius and member do not agree' % name)
+    _abi.check(lib.igan_manifold_member_nn1_update(_stream(), _ptr(query), _ptr(qnorm), _ptr(cand), _ptr(cnorm), _ptr(cand_radius),
+                                                   _ptr(member), _ptr(best_d2), _ptr(best_idx), _ptr(dots), nq, nc, dim, nk, idx_base))
+
+
 # ---- exact k-means step (csrc/kmeans.hip; the PRD metric) -------------------------------------------------------------------
 KMEANS_MAX_CLUSTERS = 64
 KMEANS_MAX_DIM = 4096

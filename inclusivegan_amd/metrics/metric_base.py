@@ -195,6 +195,75 @@ class MetricBase:
             raise ValueError('%s: the ranks disagree on the width of a %s row (%d .. %d columns)' % (type(self).__name__, what, narrowest, widest))
         return widest
 
+    def _shard_feature_rows(self, Gs, Gs_kwargs, which, rank, world):
+        """[(begin, end, features [end - begin, F])] of the 'real' or 'fake' images that rank `rank` of `world` owns, dealt the way
+        FID._shard_moments deals them (metrics with num_images / minibatch_per_gpu / feature_fn): `begin`, `end` are global image
+        indices.  Reals: a fresh walk over the data set, every rank reads the whole global minibatch and keeps its rows, so the
+        real set is the single-process one.  Fakes: `_fold_shard_fakes`.  Features must come back as device tensors: host
+        features are evaluated by one process.  A function of (rank, world) and the arguments alone."""
+        from .frechet_inception_distance import shard_slices
+        mb = self.minibatch_per_gpu
+        rows = []
+
+        def fold(begin, end, images):
+            f = self.feature_fn(images)
+            if not (torch.is_tensor(f) and f.is_cuda):
+                raise RuntimeError('%s under a process group: feature_fn must return device tensors; host (NumPy / CPU) features are '
+                                   'evaluated by one process only (run without process_group)' % type(self).__name__)
+            if f.dim() != 2 or f.shape[0] != end - begin:
+                raise ValueError('%s: feature_fn must return one row per image' % type(self).__name__)
+            rows.append((begin, end, f.to(torch.float32)))
+
+        if which == 'real':
+            if self._dataset_obj is not None:       # a fresh walk: the real set is the first num_images of the stream
+                self._dataset_obj.close()
+                self._dataset_obj = None
+            slices = shard_slices(self.num_images, mb, rank, world)
+            for g, ((begin, end), images) in enumerate(zip(slices, self._iterate_reals(minibatch_size=world * mb))):
+                if end > begin:
+                    first = g * world * mb
+                    fold(begin, end, torch.from_numpy(images[begin - first:end - first]).to(Gs.device))
+        elif which == 'fake':
+            self._fold_shard_fakes(Gs, Gs_kwargs, rank, world, fold)
+        else:
+            raise ValueError('_shard_feature_rows: which must be "real" or "fake"')
+        return rows
+
+    def _gather_shard_features(self, Gs, Gs_kwargs, which):
+        """The [num_images, F] fp32 feature matrix of the 'real' or 'fake' images on the device, the same bits on every rank of
+        the group: every rank computes the rows it owns (`_shard_feature_rows`), the shards are gathered and copied to their
+        global image indices (`gather_rows`: no sum touches a value, so -0.0 and NaN rows arrive as they were)."""
+        from .frechet_inception_distance import shard_slices
+        dist, group = torch.distributed, self._process_group
+        rank, world = dist.get_rank(group), dist.get_world_size(group)
+        rows = self._shard_feature_rows(Gs, Gs_kwargs, which, rank, world)
+        F = self._agree_on_width(rows[0][2].shape[1] if rows else 0, Gs.device, which)
+        own = torch.cat([f for _, _, f in rows]).contiguous() if rows else torch.empty([0, F], device=Gs.device, dtype=torch.float32)
+        out = torch.empty([self.num_images, F], device=Gs.device, dtype=torch.float32)
+        return gather_rows(out, [shard_slices(self.num_images, self.minibatch_per_gpu, r, world) for r in range(world)], own, group)
+
+
+def gather_rows(out, slices_by_rank, own, group):
+    """`out[begin:end]` filled for every (begin, end) of `slices_by_rank[r]`, r = 0 .. world - 1, with rank r's rows, on every
+    rank of `group`: `own` holds this rank's rows packed in the order of its slices.  Rank by rank the owner broadcasts its
+    packed rows and every rank copies them into place; a rank without rows is skipped by everyone.  Bits are moved, never
+    summed.  Every rank passes the same `slices_by_rank`."""
+    dist = torch.distributed
+    rank = dist.get_rank(group)
+    for r, slices in enumerate(slices_by_rank):
+        count = sum(end - begin for begin, end in slices)
+        if r == rank and tuple(own.shape) != (count,) + tuple(out.shape[1:]):
+            raise ValueError('gather_rows: this rank holds %s rows, its slices say %s' % (tuple(own.shape), (count,) + tuple(out.shape[1:])))
+        if count == 0:
+            continue
+        buf = own.contiguous() if r == rank else torch.empty((count,) + tuple(out.shape[1:]), device=out.device, dtype=out.dtype)
+        dist.broadcast(buf, dist.get_global_rank(group, r), group=group)
+        at = 0
+        for begin, end in slices:
+            out[begin:end] = buf[at:at + end - begin]
+            at += end - begin
+    return out
+
 
 def _retarget(kwargs):
     """The reference names its metrics `metrics.<module>.<Class>`; the same classes live under this package."""

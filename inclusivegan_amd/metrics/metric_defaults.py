@@ -1,7 +1,8 @@
 """Default metric definitions (reference: metrics/metric_defaults.py:13-29): every entry of the reference's table, and prd30k
 for the reference's stand-alone precision-recall-distributions script.  fid30k, pr50k3, prd30k, is50k and ls take the network whose pickle is not available as an injected callable (`feature_fn`, `classify_fn`,
 `classify_fns`: pass it through the metric's keyword arguments).  The five ppl* entries need no injected network: besides G
-they use the LPIPS VGG16 this package runs for the reconstruction loss."""
+they use the LPIPS VGG16 this package runs for the reconstruction loss.  Under a process group (MetricGroup.run(..., process_group=)) every
+entry but `ls` is evaluated by all ranks (`multi_rank`); `ls` runs on rank 0 alone."""
 from ..dnnlib import EasyDict
 
 metric_defaults = EasyDict([(args.name, args) for args in [

@@ -13,6 +13,11 @@ cannot decide is measured as a direct difference in fp64, so radii, predictions 
 force on the same fp32 features; nothing larger than one product block exists and nothing but the results visits the host.
 `.D` therefore holds float64 SQUARED radii (the reference: float16).
 
+Every state of the search is a function of the set of (row, index) pairs fed to it, so rows [b, e) of a pass against all
+columns are exactly rows [b, e) of the whole pass: `ManifoldEstimator.radii_rows` / `evaluate_rows` run a row range, and under
+`process_group=` every rank runs its `search_rows` of each pass and the results are gathered in rank order, which is row
+order.  Every rank passes the same feature sets and ends with the one-process state, bit for bit.
+
 The VGG-16 feature network of the reference (metrics/vgg16.pkl) is not available; `PR` takes
 `feature_fn(uint8 images [n, C, H, W] on the device) -> [n, F] array / tensor` instead, like `FID`."""
 import numpy as np
@@ -68,11 +73,29 @@ def _to_device(features):
     return out
 
 
+def search_rows(n, rank, world):
+    """The rows [begin, end) of an n-row search that rank `rank` of `world` runs: over the ranks the ranges are disjoint, in
+    rank order, cover [0, n), differ in length by at most one and may be empty."""
+    n, rank, world = int(n), int(rank), int(world)
+    if n < 0 or world < 1 or not 0 <= rank < world:
+        raise ValueError('search_rows: need n >= 0 and 0 <= rank < world')
+    return rank * n // world, (rank + 1) * n // world
+
+
+def _gather_search_rows(own, n, group):
+    """Every rank's `search_rows` slice of an n-row result -> all n rows on every rank, in rank order, which is row order."""
+    world = torch.distributed.get_world_size(group)
+    out = torch.empty((n,) + tuple(own.shape[1:]), device=own.device, dtype=own.dtype)
+    return metric_base.gather_rows(out, [[search_rows(n, r, world)] for r in range(world)], own, group)
+
+
 class ManifoldEstimator():
     """Estimate of the manifold of given feature vectors (reference :61-134): one squared radius per point and neighbourhood
     size.  `distance_block` is accepted for the reference's signature and not used (None is fine)."""
 
-    def __init__(self, distance_block, features, row_batch_size, col_batch_size, nhood_sizes, clamp_to_percentile=None):
+    def __init__(self, distance_block, features, row_batch_size, col_batch_size, nhood_sizes, clamp_to_percentile=None,
+                 process_group=None):
+        self._process_group = process_group
         self.nhood_sizes = [int(k) for k in nhood_sizes]
         self.num_nhoods = len(self.nhood_sizes)
         self._distance_block = distance_block
@@ -92,44 +115,85 @@ class ManifoldEstimator():
         self._ref_norms = hip_ops.row_sqnorm_raw(self._ref_features)
 
         # Squared distance to the k-th neighbour of every point: the kcap = max(nhood) + 1 smallest of its row.
-        state = hip_ops.knn_radius_state(num_images, max(self.nhood_sizes) + 1, self._ref_features.device)
-        self._fold_radii(state, range(0, num_images, self.col_batch_size))
-        self.D = state[:, self.nhood_sizes].cpu().numpy().astype(np.float64)
+        if process_group is None:
+            radii = self.radii_rows(0, num_images)
+        else:   # every rank its rows; all of them are in place before any membership pass needs a column's radius
+            radii = self.radii_rows(*search_rows(num_images, torch.distributed.get_rank(process_group), torch.distributed.get_world_size(process_group)))
+            radii = _gather_search_rows(radii, num_images, process_group)
+        self.D = radii.cpu().numpy().astype(np.float64)
 
         if clamp_to_percentile is not None:
             max_distances = np.percentile(self.D, clamp_to_percentile, axis=0)
             self.D[self.D > max_distances] = 0
 
-    def _fold_radii(self, state, col_starts):
+    def radii_rows(self, begin, end):
+        """The squared radii of rows [begin, end) of the feature set against ALL of it -> fp64 [end - begin, num_nhoods] on the
+        device: exactly those rows of the whole search (a row's state is a function of the set of columns fed to it).  An
+        empty range launches nothing."""
         f, n = self._ref_features, self._ref_norms
-        for begin1 in range(0, f.shape[0], self.row_batch_size):
-            end1 = begin1 + self.row_batch_size
-            for begin2 in col_starts:
+        begin, end = int(begin), int(end)
+        if not 0 <= begin <= end <= f.shape[0]:
+            raise ValueError('radii_rows: need 0 <= begin <= end <= %d' % f.shape[0])
+        state = hip_ops.knn_radius_state(end - begin, max(self.nhood_sizes) + 1, f.device)
+        for begin1 in range(begin, end, self.row_batch_size):
+            end1 = min(begin1 + self.row_batch_size, end)
+            for begin2 in range(0, f.shape[0], self.col_batch_size):
                 end2 = begin2 + self.col_batch_size
-                hip_ops.knn_radius_update_raw(f[begin1:end1], n[begin1:end1], f[begin2:end2], n[begin2:end2], state[begin1:end1])
+                hip_ops.knn_radius_update_raw(f[begin1:end1], n[begin1:end1], f[begin2:end2], n[begin2:end2], state[begin1 - begin:end1 - begin])
+        return state[:, self.nhood_sizes].contiguous()
 
-    def evaluate(self, eval_features, return_realism=False, return_neighbors=False):
-        """Are new feature vectors in the estimated manifold?  predictions int32 [m, num_nhoods] (+ realism float32 [m], nearest
-        reference index int32 [m], in the reference's four return shapes, :127-134)."""
+    def evaluate_rows(self, eval_features, begin, end, want_nn=False):
+        """Rows [begin, end) of `eval_features` against all reference rows and all radii -> (member int32 [end - begin,
+        num_nhoods], best_d2 fp64 [end - begin], best_idx int32 [end - begin]) on the device, the two last in their initial
+        state (+inf, INT32_MAX) without `want_nn`: exactly those rows of the whole evaluation.  With `want_nn` membership and
+        nearest neighbour share one product block (igan_manifold_member_nn1_update).  An empty range launches nothing."""
         ev = _to_device(eval_features)
         if ev.shape[1] != self._ref_features.shape[1]:
             raise ValueError('evaluate: feature dimension %d does not match the manifold\'s %d' % (ev.shape[1], self._ref_features.shape[1]))
+        begin, end = int(begin), int(end)
+        if not 0 <= begin <= end <= ev.shape[0]:
+            raise ValueError('evaluate_rows: need 0 <= begin <= end <= %d' % ev.shape[0])
         dev = ev.device
-        num_eval_images, num_ref_images = ev.shape[0], self._ref_features.shape[0]
+        num_ref_images = self._ref_features.shape[0]
         radii = torch.from_numpy(np.ascontiguousarray(self.D, dtype=np.float64)).to(dev)
-        want_nn = return_realism or return_neighbors
-        member = torch.zeros((num_eval_images, self.num_nhoods), device=dev, dtype=torch.int32)
-        best_d2, best_idx = hip_ops.nn1_state(num_eval_images, dev)
-        for begin1 in range(0, num_eval_images, self.row_batch_size):
-            end1 = begin1 + self.row_batch_size
+        member = torch.zeros((end - begin, self.num_nhoods), device=dev, dtype=torch.int32)
+        best_d2, best_idx = hip_ops.nn1_state(end - begin, dev)
+        for begin1 in range(begin, end, self.row_batch_size):
+            end1 = min(begin1 + self.row_batch_size, end)
+            rows = slice(begin1 - begin, end1 - begin)
             feature_batch = ev[begin1:end1]
             norms = hip_ops.row_sqnorm_raw(feature_batch)
             for begin2 in range(0, num_ref_images, self.col_batch_size):
                 end2 = begin2 + self.col_batch_size
                 ref_batch, ref_norms = self._ref_features[begin2:end2], self._ref_norms[begin2:end2]
-                hip_ops.manifold_member_update_raw(feature_batch, norms, ref_batch, ref_norms, radii[begin2:end2], member[begin1:end1])
                 if want_nn:
-                    hip_ops.nn1_update_raw(feature_batch, norms, ref_batch, ref_norms, best_d2[begin1:end1], best_idx[begin1:end1], begin2)
+                    hip_ops.manifold_member_nn1_update_raw(feature_batch, norms, ref_batch, ref_norms, radii[begin2:end2], member[rows],
+                                                           best_d2[rows], best_idx[rows], begin2)
+                else:
+                    hip_ops.manifold_member_update_raw(feature_batch, norms, ref_batch, ref_norms, radii[begin2:end2], member[rows])
+        return member, best_d2, best_idx
+
+    def evaluate(self, eval_features, return_realism=False, return_neighbors=False):
+        """Are new feature vectors in the estimated manifold?  predictions int32 [m, num_nhoods] (+ realism float32 [m], nearest
+        reference index int32 [m], in the reference's four return shapes, :127-134).  Under the estimator's process group
+        every rank passes the same `eval_features`, searches its `search_rows` and ends with all rows."""
+        ev = _to_device(eval_features)
+        want_nn = return_realism or return_neighbors
+        group = self._process_group
+        if group is None:
+            member, best_d2, best_idx = self.evaluate_rows(ev, 0, ev.shape[0], want_nn)
+        else:
+            own = search_rows(ev.shape[0], torch.distributed.get_rank(group), torch.distributed.get_world_size(group))
+            member, best_d2, best_idx = self.evaluate_rows(ev, own[0], own[1], want_nn)
+            member = _gather_search_rows(member, ev.shape[0], group)
+            if want_nn:
+                best_d2, best_idx = _gather_search_rows(best_d2, ev.shape[0], group), _gather_search_rows(best_idx, ev.shape[0], group)
+        return self.evaluation_results(member, best_d2, best_idx, return_realism, return_neighbors)
+
+    def evaluation_results(self, member, best_d2, best_idx, return_realism=False, return_neighbors=False):
+        """The host statements on the device state of all rows (`evaluate_rows`, or its row ranges concatenated in row order)
+        -> what `evaluate` returns."""
+        want_nn = return_realism or return_neighbors
         batch_predictions = member.cpu().numpy().astype(np.int32)
         if not want_nn:
             return batch_predictions
@@ -146,17 +210,19 @@ class ManifoldEstimator():
 
 
 def knn_precision_recall_features(ref_features, eval_features, feature_net=None, nhood_sizes=[3],
-                                  row_batch_size=10000, col_batch_size=10000, num_gpus=1):
+                                  row_batch_size=10000, col_batch_size=10000, num_gpus=1, process_group=None):
     """k-NN precision and recall of two sets of feature vectors (reference :138-167); NumPy arrays or device tensors [n, F].
     `feature_net` (the reference reads the feature count off it) and `num_gpus` are accepted for the reference's signature:
-    the search runs on the current device, whatever `num_gpus` says."""
+    the search runs on the current device, whatever `num_gpus` says.  `process_group`: every rank of it makes this call with
+    the same two feature sets, searches its `search_rows` of each of the four passes (two radii, two memberships) and
+    gathers the others', so every rank returns the state of the one-process call, bit for bit."""
     state = dnnlib.EasyDict()
     state.ref_features = _to_device(ref_features)
     state.eval_features = _to_device(eval_features)
 
     distance_block = DistanceBlock(state.ref_features.shape[1], num_gpus)
-    state.ref_manifold = ManifoldEstimator(distance_block, state.ref_features, row_batch_size, col_batch_size, nhood_sizes)
-    state.eval_manifold = ManifoldEstimator(distance_block, state.eval_features, row_batch_size, col_batch_size, nhood_sizes)
+    state.ref_manifold = ManifoldEstimator(distance_block, state.ref_features, row_batch_size, col_batch_size, nhood_sizes, process_group=process_group)
+    state.eval_manifold = ManifoldEstimator(distance_block, state.eval_features, row_batch_size, col_batch_size, nhood_sizes, process_group=process_group)
 
     # Precision: how many points from eval_features are in the ref_features manifold.
     state.precision, state.realism_scores, state.nearest_neighbors = state.ref_manifold.evaluate(state.eval_features, return_realism=True, return_neighbors=True)
@@ -169,6 +235,11 @@ def knn_precision_recall_features(ref_features, eval_features, feature_net=None,
 
 
 class PR(metric_base.MetricBase):
+    """Under a process group the features of both sets are collected by all ranks (MetricBase._gather_shard_features: every
+    rank ends with the same [num_images, F] matrices) and the four passes of the search are spread over them by rows."""
+
+    multi_rank = True
+
     def __init__(self, num_images, nhood_size, minibatch_per_gpu, row_batch_size, col_batch_size, feature_fn=None, **kwargs):
         super().__init__(**kwargs)
         self.num_images = num_images
@@ -186,6 +257,23 @@ class PR(metric_base.MetricBase):
     def _evaluate(self, Gs, Gs_kwargs, num_gpus):
         if self.feature_fn is None:
             raise RuntimeError('PR needs feature_fn: the reference\'s metrics/vgg16.pkl is not available in this tree')
+        if self._process_group is not None:
+            if self._real_features is None:
+                self._real_features = self._gather_shard_features(Gs, Gs_kwargs, 'real')
+            ref_features = self._real_features
+            eval_features = self._gather_shard_features(Gs, Gs_kwargs, 'fake')
+        else:
+            ref_features, eval_features = self._collect_features(Gs, Gs_kwargs, num_gpus)
+
+        # Precision and recall (the reference passes row_batch_size for both batch sizes, :219-220).
+        state = knn_precision_recall_features(ref_features=ref_features, eval_features=eval_features, nhood_sizes=[self.nhood_size],
+                                              row_batch_size=self.row_batch_size, col_batch_size=self.row_batch_size, num_gpus=num_gpus,
+                                              process_group=self._process_group)
+        self._report_result(state.knn_precision[0], suffix='_precision')
+        self._report_result(state.knn_recall[0], suffix='_recall')
+
+    def _collect_features(self, Gs, Gs_kwargs, num_gpus):
+        """One process: the features of `num_images` reals (cached per object) and fakes."""
         minibatch_size = num_gpus * self.minibatch_per_gpu
 
         # Features of the reals, cached per object.
@@ -208,9 +296,4 @@ class PR(metric_base.MetricBase):
         for begin in range(0, self.num_images, minibatch_size):
             end = min(begin + minibatch_size, self.num_images)
             eval_features[begin:end] = self._features(self._generate(Gs, minibatch_size, Gs_kwargs), Gs.device)[:end - begin]
-
-        # Precision and recall (the reference passes row_batch_size for both batch sizes, :219-220).
-        state = knn_precision_recall_features(ref_features=ref_features, eval_features=eval_features, nhood_sizes=[self.nhood_size],
-                                              row_batch_size=self.row_batch_size, col_batch_size=self.row_batch_size, num_gpus=num_gpus)
-        self._report_result(state.knn_precision[0], suffix='_precision')
-        self._report_result(state.knn_recall[0], suffix='_recall')
+        return ref_features, eval_features

@@ -33,7 +33,7 @@ def _with_injected(metric_args, inject):
 
 def run(network_pkl, metrics, dataset, data_dir, mirror_augment, num_gpus=1, run_dir=None, inject=None, process_group=None):
     """`process_group` None: this process evaluates everything (`num_gpus` scales the minibatch on its one device).  A group: every
-    rank makes this call; metrics that spread over ranks (fid*) do, the others run on rank 0; pass `run_dir` on rank 0 only."""
+    rank makes this call; metrics that spread over ranks (every one but ls) do, the others run on rank 0; pass `run_dir` on rank 0 only."""
     if process_group is None or run_dir is not None:
         print('Evaluating metrics "%s" for "%s"...' % (','.join(metrics), network_pkl))
     network_pkl = pretrained_networks.get_path_or_url(network_pkl)

@@ -164,8 +164,8 @@ def main():
     if world > 1:
         os.environ.setdefault('MASTER_ADDR', '127.0.0.1')
         import datetime
-        # generous timeout: the snapshot metrics that do not spread over the ranks (all but fid*, mode_counts*, KL* and is*; every one under IGAN_METRICS_RANKS=0) run on
-        # rank 0 alone while the other ranks wait at a collective
+        # generous timeout: the snapshot metric that does not spread over the ranks (ls; every metric under IGAN_METRICS_RANKS=0) runs on rank 0 alone
+        # while the other ranks wait at a collective
         torch.distributed.init_process_group('nccl', timeout=datetime.timedelta(hours=4))
     assert world == args.num_gpus, 'one process per GPU: launch %d ranks' % args.num_gpus
     run(**vars(args))

@@ -6,6 +6,10 @@ same passes in a plain torch formulation in the same process: the fp32 `mm` canc
 on row blocks, `kthvalue` for the radii and `<=` / `any` for the membership.  The number of predictions on which the two
 disagree is reported (the HIP path is exact; the torch one decides near-boundary pairs by fp32 rounding).
 
+The precision pass is timed in two forms, alternating in the same repetitions: as `evaluate` runs it, membership and nearest
+neighbour on ONE product block per batch (igan_manifold_member_nn1_update), and as the pair of calls it replaced
+(igan_manifold_member_update + igan_nn1_update: the product block twice).  Their results are compared bit for bit.
+
     python tools/pr_bench.py [--n 50000] [--dim 4096] [--k 3] [--rows 10000] [--cols 10000] [--reps 2] [--out FILE]"""
 import argparse
 import os
@@ -46,6 +50,25 @@ def torch_member(ref, radii, ev, rows):
     return out
 
 
+def two_product_precision(m, ev):
+    """The precision pass as the pair of calls per batch: what ManifoldEstimator.evaluate ran before the one-product entry."""
+    from inclusivegan_amd import hip_ops
+    dev = ev.device
+    radii = torch.from_numpy(np.ascontiguousarray(m.D, dtype=np.float64)).to(dev)
+    member = torch.zeros((ev.shape[0], m.num_nhoods), device=dev, dtype=torch.int32)
+    best_d2, best_idx = hip_ops.nn1_state(ev.shape[0], dev)
+    for b1 in range(0, ev.shape[0], m.row_batch_size):
+        e1 = b1 + m.row_batch_size
+        batch = ev[b1:e1]
+        norms = hip_ops.row_sqnorm_raw(batch)
+        for b2 in range(0, m._ref_features.shape[0], m.col_batch_size):
+            e2 = b2 + m.col_batch_size
+            rb, rn = m._ref_features[b2:e2], m._ref_norms[b2:e2]
+            hip_ops.manifold_member_update_raw(batch, norms, rb, rn, radii[b2:e2], member[b1:e1])
+            hip_ops.nn1_update_raw(batch, norms, rb, rn, best_d2[b1:e1], best_idx[b1:e1], b2)
+    return m.evaluation_results(member, best_d2, best_idx, True, True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--n', type=int, default=50000)
@@ -65,6 +88,7 @@ def main():
     print(lines[0], flush=True)
     hip = {name: [] for name in ('ref radii', 'eval radii', 'precision (+ nearest)', 'recall')}
     tor = {name: [] for name in hip}
+    two = []
     for rep in range(a.reps):
         t, m_ref = timed(lambda: PR.ManifoldEstimator(None, ref, a.rows, a.cols, [a.k]));              hip['ref radii'].append(t)
         t, t_ref = timed(lambda: torch_radii(ref, a.k, a.rows));                                        tor['ref radii'].append(t)
@@ -72,12 +96,17 @@ def main():
         t, t_ev = timed(lambda: torch_radii(ev, a.k, a.rows));                                          tor['eval radii'].append(t)
         t, (prec, realism, nearest) = timed(lambda: m_ref.evaluate(ev, return_realism=True, return_neighbors=True)); hip['precision (+ nearest)'].append(t)
         t, t_prec = timed(lambda: torch_member(ref, t_ref, ev, a.rows));                                tor['precision (+ nearest)'].append(t)
+        t, old_form = timed(lambda: two_product_precision(m_ref, ev));                                  two.append(t)
+        same_bits = all(x.tobytes() == y.tobytes() for x, y in zip((prec, realism, nearest), old_form))
         t, rec = timed(lambda: m_ev.evaluate(ref));                                                     hip['recall'].append(t)
         t, t_rec = timed(lambda: torch_member(ev, t_ev, ref, a.rows));                                  tor['recall'].append(t)
         print('rep %d done' % rep, flush=True)
     lines.append('%-24s %-28s %-28s' % ('pass', 'HIP exact search, s per rep', 'torch fp32 mm form, s per rep'))
     for name in hip:
         lines.append('%-24s %-28s %-28s' % (name, ' '.join('%.3f' % t for t in hip[name]), ' '.join('%.3f' % t for t in tor[name])))
+    lines.append('%-24s %-28s %-28s' % ('  as two calls, 2 products', ' '.join('%.3f' % t for t in two), '-'))
+    lines.append('precision pass: one product block %.3f s, two product blocks %.3f s (best rep each); results bit-identical: %s'
+                 % (min(hip['precision (+ nearest)']), min(two), same_bits))
     lines.append('%-24s %-28s %-28s' % ('total (best rep each)', '%.3f' % sum(min(v) for v in hip.values()), '%.3f' % sum(min(v) for v in tor.values())))
     t_prec, t_rec = t_prec.cpu().numpy(), t_rec.cpu().numpy()
     lines.append('knn_precision: HIP %.6f torch %.6f   knn_recall: HIP %.6f torch %.6f' % (prec.mean(), t_prec.mean(), rec.mean(), t_rec.mean()))
