@@ -10,12 +10,13 @@ fp64 sum of p log p, in a fixed order), and a split's score is  exp(plogp / n - 
 reference's statement with the mean over the images taken first.  NumPy / CPU results are collected on the host and go
 through the reference's statement, value for value.
 
-Under a process group (`run(..., process_group=)`) the images are dealt to the ranks as FID deals them
-(`MetricBase._fold_shard_fakes`); a row's split is decided by its GLOBAL index, every rank folds its rows,
+Under a process group (`run(..., process_group=)`) the images are dealt to the ranks (`MetricBase._walk`); a row's split is
+decided by its GLOBAL index, every rank folds its rows,
 `SplitProbStats.all_merge` leaves every rank with the same bits and rank 0 reports.  Host results are REFUSED under a group."""
 import numpy as np
 import torch
 
+from .. import hip_ops
 from . import metric_base
 
 
@@ -42,26 +43,27 @@ class IS(metric_base.MetricBase):
         self.minibatch_per_gpu = minibatch_per_gpu
         self.classify_fn = classify_fn
 
+    def _folded(self, stats, begin, probs):
+        """`stats` (None: a new hip_ops.SplitProbStats) with one minibatch of device probabilities folded in, cast to float32 as
+        the host path casts it."""
+        if stats is None:
+            stats = hip_ops.SplitProbStats(probs.shape[1], self.num_images, self.num_splits, probs.device)
+        stats.update(probs.detach().to(torch.float32), begin)
+        return stats
+
     def _shard_stats(self, Gs, Gs_kwargs, rank, world):
         """hip_ops.SplitProbStats of the fakes rank `rank` of `world` owns, or None when it owns none -- a function of its
-        arguments alone (MetricBase._fold_shard_fakes), so one process can rebuild every rank's state."""
-        from .. import hip_ops
-        state = []
+        arguments alone (MetricBase._walk), so one process can rebuild every rank's state."""
+        stats = None
 
-        def fold(begin, end, images):
-            probs = self.classify_fn(images)
-            if not (torch.is_tensor(probs) and probs.is_cuda):
-                raise RuntimeError('IS under a process group: classify_fn must return device tensors; host (NumPy / CPU) results are '
-                                   'evaluated by one process only (run without process_group)')
-            if not state:
-                state.append(hip_ops.SplitProbStats(probs.shape[1], self.num_images, self.num_splits, probs.device))
-            state[0].update(probs.detach().to(torch.float32), begin)
+        def fold(begin, end, probs):
+            nonlocal stats
+            stats = self._folded(stats, begin, self._device_result(probs, 'classify_fn'))
 
-        self._fold_shard_fakes(Gs, Gs_kwargs, rank, world, fold)
-        return state[0] if state else None
+        self._walk(Gs, Gs_kwargs, 'fake', self.classify_fn, fold, 'images', shard=(rank, world))
+        return stats
 
     def _evaluate_sharded(self, Gs, Gs_kwargs):
-        from .. import hip_ops
         group = self._process_group
         rank, world = torch.distributed.get_rank(group), torch.distributed.get_world_size(group)
         stats = self._shard_stats(Gs, Gs_kwargs, rank, world)
@@ -78,26 +80,22 @@ class IS(metric_base.MetricBase):
             raise RuntimeError('IS needs classify_fn: the reference\'s metrics/inception_v3_softmax.pkl is not available in this tree')
         if self._process_group is not None:
             return self._evaluate_sharded(Gs, Gs_kwargs)
-        minibatch_size = num_gpus * self.minibatch_per_gpu
         activations = stats = None
 
         # Calculate activations for fakes.
-        for begin in range(0, self.num_images, minibatch_size):
-            end = min(begin + minibatch_size, self.num_images)
-            probs = self.classify_fn(self._generate(Gs, minibatch_size, Gs_kwargs))
+        def fold(begin, end, probs):
+            nonlocal activations, stats
             on_device = torch.is_tensor(probs) and probs.is_cuda
-            if begin and on_device != (stats is not None):
-                raise RuntimeError('IS: classify_fn must return device tensors for every minibatch or for none')
+            self._same_kind(begin == 0, on_device, stats is not None, 'classify_fn')
             if on_device:
-                if stats is None:
-                    from .. import hip_ops
-                    stats = hip_ops.SplitProbStats(probs.shape[1], self.num_images, self.num_splits, probs.device)
-                stats.update(probs.detach().to(torch.float32)[:end - begin], begin)
-                continue
+                stats = self._folded(stats, begin, probs)
+                return
             probs = torch.as_tensor(probs).detach().to('cpu', torch.float32).numpy()
             if activations is None:
                 activations = np.empty([self.num_images, probs.shape[1]], dtype=np.float32)
-            activations[begin:end] = probs[:end - begin]
+            activations[begin:end] = probs
+
+        self._walk(Gs, Gs_kwargs, 'fake', self.classify_fn, fold, 'result', num_gpus=num_gpus)
 
         # Calculate IS.
         scores = stats.scores() if stats is not None else inception_score_splits(activations, self.num_splits)

@@ -7,6 +7,7 @@ takes the network that turns uint8 images into features / logits as an INJECTED 
 the statistics on top of them (the FID formula, mode count, KL to uniform) are the reference's, value for value
 (tests/test_metrics.py pins them to the reference's own statements).  Fakes come from Gs on this engine's HIP path.
 """
+import contextlib
 import hashlib
 import os
 import time
@@ -22,6 +23,23 @@ def convert_images_to_uint8(images, drange=[-1, 1], nchw_to_nhwc=False, shrink=1
     """float images -> uint8 with the reference's rounding (dnnlib/tflib/tfutil.py:255-267: scale, + 0.5, saturating cast):
     tflib.convert_images_to_uint8 -- one HIP kernel for a device tensor, the torch statement for a CPU tensor."""
     return tfutil.convert_images_to_uint8(images, drange=drange, nchw_to_nhwc=nchw_to_nhwc, shrink=shrink)
+
+
+def shard_slices(num_images, minibatch_per_gpu, rank, world):
+    """The image rows rank `rank` of `world` owns, one (begin, end) per global minibatch: global minibatch g covers images
+    [g world mb, (g + 1) world mb) cut at num_images, and the rank owns rows [rank mb, (rank + 1) mb) of it, cut the same way
+    (begin == end: the rank sits this minibatch out).  Over the ranks the slices are disjoint and cover [0, num_images)."""
+    num_images, mb, rank, world = int(num_images), int(minibatch_per_gpu), int(rank), int(world)
+    if mb < 1 or world < 1 or not 0 <= rank < world or num_images < 0:
+        raise ValueError('shard_slices: need minibatch_per_gpu >= 1, 0 <= rank < world and num_images >= 0')
+    out = []
+    for start in range(0, num_images, world * mb):
+        begin = min(start + rank * mb, num_images)
+        out.append((begin, min(begin + mb, num_images)))
+    return out
+
+
+SHARD_SEED = 0x51d0     # latents and noise of rank r under a process group: a private device generator seeded SHARD_SEED + r
 
 
 class _Result:
@@ -167,21 +185,74 @@ class MetricBase:
         images = Gs.get_output_for(latents, labels, **Gs_kwargs)
         return convert_images_to_uint8(images) if as_uint8 else images
 
-    # ---- under a process group (metrics with num_images / minibatch_per_gpu) -------------------------------------------------
-    def _fold_shard_fakes(self, Gs, Gs_kwargs, rank, world, fold, as_uint8=True):
-        """`fold(begin, end, images)` for the fakes of every global minibatch that rank `rank` of `world` owns, the way
-        FID._shard_moments deals them: a global minibatch is world x minibatch_per_gpu images, the rank owns rows [rank mb,
-        (rank + 1) mb) of it (frechet_inception_distance.shard_slices; the last slice is cut at num_images and may be empty),
-        labels are drawn for the global minibatch and sliced, latents and noise come from a private device generator seeded
-        SHARD_SEED + rank.  A function of (rank, world) and the arguments alone: one process can replay every rank."""
-        from .frechet_inception_distance import SHARD_SEED, shard_slices
-        mb = self.minibatch_per_gpu
-        self._label_rng = None
-        with tfutil.use_random(tfutil.SeededRandom(Gs.device, SHARD_SEED + rank)):
-            for begin, end in shard_slices(self.num_images, mb, rank, world):
-                labels = self._get_random_labels(world * mb, Gs)[rank * mb:(rank + 1) * mb]
+    # ---- the one walk over reals and fakes (metrics with num_images / minibatch_per_gpu) ------------------------------------
+    def _walk(self, Gs, Gs_kwargs, which, net, fold, fakes_cut, num_gpus=1, shard=None, as_uint8=True):
+        """`fold(begin, end, net(images))` for every minibatch of the `num_images` 'real' or 'fake' images this process owns;
+        `begin`, `end` are global image indices.  `fold` is called from inside the walk, which is no generator: the private
+        random source of a sharded walk ends with the walk, also when `net` or `fold` raises.
+
+        `shard` None -- one process: minibatches of num_gpus x minibatch_per_gpu images.  The reals continue the data set
+        object that run() configured, the fakes draw from the process's random source and `_generate` draws their labels.
+
+        `shard` (rank, world) -- the dealing under a process group, the towers of the reference's per-GPU graphs: a global
+        minibatch is world x minibatch_per_gpu images and the rank owns rows [rank mb, (rank + 1) mb) of it (`shard_slices`;
+        the last slice is cut at num_images and may be empty).  Reals: a fresh walk over the data set, every rank reads the
+        whole global minibatch (the host read is redundant per rank) and keeps its rows, so the real set is the one-process
+        one.  Fakes: the label stream restarts at its seed, labels are drawn for the whole global minibatch -- also by a rank
+        that sits it out -- and sliced; latents and noise come from a private device generator seeded SHARD_SEED + rank, so
+        no two ranks draw the same fakes and the process's device stream is left alone.  A function of (rank, world) and the
+        arguments alone: one process can replay every rank.
+
+        Where the ragged last minibatch is cut is today's, case by case, and not consistent:
+
+            path                                       reals                         fakes
+            one process, all six metrics               images cut to end - begin     `net` sees the whole minibatch, its RESULT
+                                                       before `net`                  is cut (the reference's statement)
+            group, FID                                 images cut                    whole minibatch, result cut
+            group, IS / mode_counts / KL / PR / PRD    images cut                    images cut before `net`
+
+        Reals are always cut before `net`; `fakes_cut` is 'result' or 'images'.  The last two rows differ because the dealing
+        was written twice; making them agree moves bits wherever world x minibatch_per_gpu does not divide num_images (50 000
+        images, 8 per GPU), so it is left as found."""
+        if which not in ('real', 'fake') or fakes_cut not in ('result', 'images'):
+            raise ValueError('%s._walk: which must be "real" or "fake", fakes_cut "result" or "images"' % type(self).__name__)
+        sharded = shard is not None
+        rank, world = shard if sharded else (0, 1)
+        mb = self.minibatch_per_gpu * (1 if sharded else num_gpus)
+        slices = shard_slices(self.num_images, mb, rank, world)
+        if which == 'real':
+            if sharded and self._dataset_obj is not None:       # a fresh walk: the real set is the first num_images of the stream
+                self._dataset_obj.close()
+                self._dataset_obj = None
+            for (begin, end), images in zip(slices, self._iterate_reals(minibatch_size=world * mb)):
                 if end > begin:
-                    fold(begin, end, self._generate(Gs, mb, Gs_kwargs, as_uint8=as_uint8, labels=labels)[:end - begin])
+                    fold(begin, end, net(torch.from_numpy(images[rank * mb:rank * mb + end - begin]).to(Gs.device)))
+            return
+        if sharded:
+            self._label_rng = None
+        with tfutil.use_random(tfutil.SeededRandom(Gs.device, SHARD_SEED + rank)) if sharded else contextlib.nullcontext():
+            for begin, end in slices:
+                labels = dict(labels=self._get_random_labels(world * mb, Gs)[rank * mb:(rank + 1) * mb]) if sharded else {}
+                if end > begin:
+                    images = self._generate(Gs, mb, Gs_kwargs, as_uint8=as_uint8, **labels)
+                    fold(begin, end, net(images)[:end - begin] if fakes_cut == 'result' else net(images[:end - begin]))
+
+    def _fold_shard_fakes(self, Gs, Gs_kwargs, rank, world, fold, as_uint8=True):
+        """`fold(begin, end, images)` for the fakes of every global minibatch that rank `rank` of `world` owns (`_walk`)."""
+        self._walk(Gs, Gs_kwargs, 'fake', lambda images: images, fold, 'images', shard=(rank, world), as_uint8=as_uint8)
+
+    # ---- what a network may return ------------------------------------------------------------------------------------------
+    def _device_result(self, result, fn_name, dtype=None):
+        """`result` of `fn_name` (feature_fn / classify_fn) under a process group: a device tensor (of `dtype`), or the refusal."""
+        if not (torch.is_tensor(result) and result.is_cuda and dtype in (None, result.dtype)):
+            raise RuntimeError('%s under a process group: %s must return device tensors%s; host (NumPy / CPU) results are evaluated by '
+                               'one process only (run without process_group)' % (type(self).__name__, fn_name, ' of %s' % dtype if dtype else ''))
+        return result
+
+    def _same_kind(self, first, on_device, so_far, fn_name, kind='device tensors'):
+        """One process: a minibatch's result is on the device (`on_device`) exactly when the earlier ones were (`so_far`)."""
+        if not first and on_device != so_far:
+            raise RuntimeError('%s: %s must return %s for every minibatch or for none' % (type(self).__name__, fn_name, kind))
 
     def _agree_on_width(self, K, device, what):
         """The one row width K of all ranks of the group; a rank without rows passes 0 and learns it here (all-reduce MAX).
@@ -195,45 +266,25 @@ class MetricBase:
             raise ValueError('%s: the ranks disagree on the width of a %s row (%d .. %d columns)' % (type(self).__name__, what, narrowest, widest))
         return widest
 
+    # ---- feature matrices (metrics with feature_fn) ---------------------------------------------------------------------------
     def _shard_feature_rows(self, Gs, Gs_kwargs, which, rank, world):
-        """[(begin, end, features [end - begin, F])] of the 'real' or 'fake' images that rank `rank` of `world` owns, dealt the way
-        FID._shard_moments deals them (metrics with num_images / minibatch_per_gpu / feature_fn): `begin`, `end` are global image
-        indices.  Reals: a fresh walk over the data set, every rank reads the whole global minibatch and keeps its rows, so the
-        real set is the single-process one.  Fakes: `_fold_shard_fakes`.  Features must come back as device tensors: host
-        features are evaluated by one process.  A function of (rank, world) and the arguments alone."""
-        from .frechet_inception_distance import shard_slices
-        mb = self.minibatch_per_gpu
+        """[(begin, end, features [end - begin, F])] of the 'real' or 'fake' images that rank `rank` of `world` owns (`_walk`).
+        Features must come back as device tensors: host features are evaluated by one process."""
         rows = []
 
-        def fold(begin, end, images):
-            f = self.feature_fn(images)
-            if not (torch.is_tensor(f) and f.is_cuda):
-                raise RuntimeError('%s under a process group: feature_fn must return device tensors; host (NumPy / CPU) features are '
-                                   'evaluated by one process only (run without process_group)' % type(self).__name__)
+        def fold(begin, end, f):
+            f = self._device_result(f, 'feature_fn')
             if f.dim() != 2 or f.shape[0] != end - begin:
                 raise ValueError('%s: feature_fn must return one row per image' % type(self).__name__)
             rows.append((begin, end, f.to(torch.float32)))
 
-        if which == 'real':
-            if self._dataset_obj is not None:       # a fresh walk: the real set is the first num_images of the stream
-                self._dataset_obj.close()
-                self._dataset_obj = None
-            slices = shard_slices(self.num_images, mb, rank, world)
-            for g, ((begin, end), images) in enumerate(zip(slices, self._iterate_reals(minibatch_size=world * mb))):
-                if end > begin:
-                    first = g * world * mb
-                    fold(begin, end, torch.from_numpy(images[begin - first:end - first]).to(Gs.device))
-        elif which == 'fake':
-            self._fold_shard_fakes(Gs, Gs_kwargs, rank, world, fold)
-        else:
-            raise ValueError('_shard_feature_rows: which must be "real" or "fake"')
+        self._walk(Gs, Gs_kwargs, which, self.feature_fn, fold, 'images', shard=(rank, world))
         return rows
 
     def _gather_shard_features(self, Gs, Gs_kwargs, which):
         """The [num_images, F] fp32 feature matrix of the 'real' or 'fake' images on the device, the same bits on every rank of
         the group: every rank computes the rows it owns (`_shard_feature_rows`), the shards are gathered and copied to their
         global image indices (`gather_rows`: no sum touches a value, so -0.0 and NaN rows arrive as they were)."""
-        from .frechet_inception_distance import shard_slices
         dist, group = torch.distributed, self._process_group
         rank, world = dist.get_rank(group), dist.get_world_size(group)
         rows = self._shard_feature_rows(Gs, Gs_kwargs, which, rank, world)
@@ -241,6 +292,22 @@ class MetricBase:
         own = torch.cat([f for _, _, f in rows]).contiguous() if rows else torch.empty([0, F], device=Gs.device, dtype=torch.float32)
         out = torch.empty([self.num_images, F], device=Gs.device, dtype=torch.float32)
         return gather_rows(out, [shard_slices(self.num_images, self.minibatch_per_gpu, r, world) for r in range(world)], own, group)
+
+    def _feature_matrix(self, Gs, Gs_kwargs, which, num_gpus):
+        """The [num_images, F] fp32 matrix of `feature_fn` of the 'real' or 'fake' images, on the device: gathered from all
+        ranks under a process group, collected minibatch by minibatch in one process (host features are moved over)."""
+        if self._process_group is not None:
+            return self._gather_shard_features(Gs, Gs_kwargs, which)
+        out = []
+
+        def fold(begin, end, f):
+            f = torch.as_tensor(f).to(Gs.device, torch.float32)
+            if not out:
+                out.append(torch.empty([self.num_images, f.shape[1]], device=Gs.device, dtype=torch.float32))
+            out[0][begin:end] = f
+
+        self._walk(Gs, Gs_kwargs, which, self.feature_fn, fold, 'result', num_gpus=num_gpus)
+        return out[0]
 
 
 def gather_rows(out, slices_by_rank, own, group):

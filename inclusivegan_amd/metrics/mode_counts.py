@@ -9,10 +9,9 @@ Logits that come back as float32 device tensors stay on the device: every miniba
 `KL.kl_from_counts`).  Any other result -- NumPy, a CPU tensor, another dtype -- goes through np.argmax on the host, the
 reference's statements.
 
-Under a process group (`run(..., process_group=)`) the images are dealt to the ranks as FID deals them
-(`MetricBase._fold_shard_fakes`), every rank folds its rows into its own histogram, one all_reduce(SUM) of the int64 counts
-gives every rank the exact total and rank 0 reports.  Host results are REFUSED under a group: they are evaluated by one
-process."""
+Under a process group (`run(..., process_group=)`) the images are dealt to the ranks (`MetricBase._walk`), every rank folds
+its rows into its own histogram, one all_reduce(SUM) of the int64 counts gives every rank the exact total and rank 0 reports.
+Host results are REFUSED under a group: they are evaluated by one process."""
 import numpy as np
 
 from . import metric_base
@@ -36,18 +35,22 @@ def _resolve_classifier(metric):
                        'Train this project\'s own classifier with `python -m inclusivegan_amd.train_classifier`.' % metric.name)
 
 
-def predicted_labels(metric, Gs, Gs_kwargs, num_gpus):
+def _host(logits):
     import torch
+    return logits.detach().cpu().numpy() if torch.is_tensor(logits) else np.asarray(logits)
+
+
+def predicted_labels(metric, Gs, Gs_kwargs, num_gpus):
     _resolve_classifier(metric)
-    minibatch_size = num_gpus * metric.minibatch_per_gpu
     labels_all = np.empty([metric.num_images], dtype=np.float32)
     num_classes = None
-    for begin in range(0, metric.num_images, minibatch_size):
-        end = min(begin + minibatch_size, metric.num_images)
-        logits = metric.classify_fn(metric._generate(Gs, minibatch_size, Gs_kwargs, as_uint8=False))     # the classifier sees G's float output (:39-40)
-        logits = logits.detach().cpu().numpy() if torch.is_tensor(logits) else np.asarray(logits)
+
+    def fold(begin, end, logits):
+        nonlocal num_classes
         num_classes = logits.shape[1]
-        labels_all[begin:end] = np.argmax(logits, axis=1)[:end - begin]
+        labels_all[begin:end] = np.argmax(_host(logits), axis=1)
+
+    metric._walk(Gs, Gs_kwargs, 'fake', metric.classify_fn, fold, 'result', num_gpus=num_gpus, as_uint8=False)     # the classifier sees G's float output (:39-40)
     return labels_all, num_classes
 
 
@@ -72,48 +75,45 @@ def _on_device_f32(logits):
 def class_statistics(metric, Gs, Gs_kwargs, num_gpus):
     """One process, the draws of `predicted_labels`: float32 device logits are folded on the device -> (counts [K] NumPy
     integers, None, K); anything else is labelled on the host as there -> (None, labels_all, K)."""
-    import torch
     from .. import hip_ops
     _resolve_classifier(metric)
-    minibatch_size = num_gpus * metric.minibatch_per_gpu
     hist = labels_all = num_classes = None
-    for begin in range(0, metric.num_images, minibatch_size):
-        end = min(begin + minibatch_size, metric.num_images)
-        logits = metric.classify_fn(metric._generate(Gs, minibatch_size, Gs_kwargs, as_uint8=False))     # the classifier sees G's float output (:39-40)
+
+    def fold(begin, end, logits):
+        nonlocal hist, labels_all, num_classes
         on_device = _on_device_f32(logits)
-        if begin and on_device != (hist is not None):
-            raise RuntimeError('%s: classify_fn must return float32 device tensors for every minibatch or for none' % metric.name)
+        metric._same_kind(begin == 0, on_device, hist is not None, 'classify_fn', 'float32 device tensors')
         if on_device:
             if hist is None:
                 hist = hip_ops.ClassHistogram(logits.shape[1], logits.device)
-            hist.update(logits[:end - begin])
+            hist.update(logits)
         else:
-            logits = logits.detach().cpu().numpy() if torch.is_tensor(logits) else np.asarray(logits)
             if labels_all is None:
                 labels_all = np.empty([metric.num_images], dtype=np.float32)
             num_classes = logits.shape[1]
-            labels_all[begin:end] = np.argmax(logits, axis=1)[:end - begin]
+            labels_all[begin:end] = np.argmax(_host(logits), axis=1)
+
+    metric._walk(Gs, Gs_kwargs, 'fake', metric.classify_fn, fold, 'result', num_gpus=num_gpus, as_uint8=False)     # the classifier sees G's float output (:39-40)
     return (hist.to_host(), None, hist.K) if hist is not None else (None, labels_all, num_classes)
 
 
 def shard_histogram(metric, Gs, Gs_kwargs, rank, world):
     """hip_ops.ClassHistogram of the fakes rank `rank` of `world` owns, or None when it owns none -- a function of its
-    arguments alone (MetricBase._fold_shard_fakes), so one process can rebuild every rank's state."""
+    arguments alone (MetricBase._walk), so one process can rebuild every rank's state."""
+    import torch
     from .. import hip_ops
     _resolve_classifier(metric)
-    state = []
+    hist = None
 
-    def fold(begin, end, images):
-        logits = metric.classify_fn(images)
-        if not _on_device_f32(logits):
-            raise RuntimeError('%s under a process group: classify_fn must return float32 device tensors; host (NumPy / CPU) results are '
-                               'evaluated by one process only (run without process_group)' % type(metric).__name__)
-        if not state:
-            state.append(hip_ops.ClassHistogram(logits.shape[1], logits.device))
-        state[0].update(logits)
+    def fold(begin, end, logits):
+        nonlocal hist
+        logits = metric._device_result(logits, 'classify_fn', torch.float32)
+        if hist is None:
+            hist = hip_ops.ClassHistogram(logits.shape[1], logits.device)
+        hist.update(logits)
 
-    metric._fold_shard_fakes(Gs, Gs_kwargs, rank, world, fold, as_uint8=False)
-    return state[0] if state else None
+    metric._walk(Gs, Gs_kwargs, 'fake', metric.classify_fn, fold, 'images', shard=(rank, world), as_uint8=False)
+    return hist
 
 
 def merged_class_counts(metric, Gs, Gs_kwargs):

@@ -240,7 +240,7 @@ def prd_to_max_f_beta_pair(precision, recall, beta=8):
 
 
 class PRD(metric_base.MetricBase):
-    """Under a process group the features of both sets are collected by all ranks (MetricBase._gather_shard_features) and
+    """Under a process group the features of both sets are collected by all ranks (MetricBase._feature_matrix) and
     every rank ends with the same two matrices in the same row order.  The clustering depends on that order and on one seeded
     RandomState, so every rank runs it and gets the same numbers; nothing is broadcast from rank 0."""
 
@@ -257,51 +257,16 @@ class PRD(metric_base.MetricBase):
         self.seed = seed
         self._real_features = None
 
-    def _features(self, images, device):
-        import torch
-        f = self.feature_fn(images)
-        return torch.as_tensor(f).to(device, torch.float32)          # features stay on the device
-
     def _evaluate(self, Gs, Gs_kwargs, num_gpus):
         if self.feature_fn is None:
             raise RuntimeError('PRD needs feature_fn: the reference\'s precision-recall-distributions/inception.pb is not available in this tree')
-        if self._process_group is not None:
-            if self._real_features is None:
-                self._real_features = self._gather_shard_features(Gs, Gs_kwargs, 'real')
-            ref_features = self._real_features
-            eval_features = self._gather_shard_features(Gs, Gs_kwargs, 'fake')
-        else:
-            ref_features, eval_features = self._collect_features(Gs, Gs_kwargs, num_gpus)
+        if self._real_features is None:      # cached per object
+            self._real_features = self._feature_matrix(Gs, Gs_kwargs, 'real', num_gpus)
+        ref_features = self._real_features
+        eval_features = self._feature_matrix(Gs, Gs_kwargs, 'fake', num_gpus)
 
         precision, recall = compute_prd_from_embedding(eval_features, ref_features, num_clusters=self.num_clusters,
                                                        num_angles=self.num_angles, num_runs=self.num_runs, seed=self.seed)
         f_beta, f_beta_inv = prd_to_max_f_beta_pair(precision, recall, beta=8)
         self._report_result(f_beta, suffix='_F8')
         self._report_result(f_beta_inv, suffix='_F1_8')
-
-    def _collect_features(self, Gs, Gs_kwargs, num_gpus):
-        """One process: the features of `num_images` reals (cached per object) and fakes."""
-        import torch
-        minibatch_size = num_gpus * self.minibatch_per_gpu
-
-        # Features of the reals, cached per object.
-        if self._real_features is None:
-            ref_features = None
-            for idx, images in enumerate(self._iterate_reals(minibatch_size=minibatch_size)):
-                begin = idx * minibatch_size
-                end = min(begin + minibatch_size, self.num_images)
-                f = self._features(torch.from_numpy(images[:end - begin]).to(Gs.device), Gs.device)
-                if ref_features is None:
-                    ref_features = torch.empty([self.num_images, f.shape[1]], device=Gs.device, dtype=torch.float32)
-                ref_features[begin:end] = f
-                if end == self.num_images:
-                    break
-            self._real_features = ref_features
-        ref_features = self._real_features
-
-        # Features of the fakes.
-        eval_features = torch.empty_like(ref_features)
-        for begin in range(0, self.num_images, minibatch_size):
-            end = min(begin + minibatch_size, self.num_images)
-            eval_features[begin:end] = self._features(self._generate(Gs, minibatch_size, Gs_kwargs), Gs.device)[:end - begin]
-        return ref_features, eval_features

@@ -235,8 +235,8 @@ def knn_precision_recall_features(ref_features, eval_features, feature_net=None,
 
 
 class PR(metric_base.MetricBase):
-    """Under a process group the features of both sets are collected by all ranks (MetricBase._gather_shard_features: every
-    rank ends with the same [num_images, F] matrices) and the four passes of the search are spread over them by rows."""
+    """Under a process group the features of both sets are collected by all ranks (MetricBase._feature_matrix: every rank
+    ends with the same [num_images, F] matrices) and the four passes of the search are spread over them by rows."""
 
     multi_rank = True
 
@@ -250,20 +250,13 @@ class PR(metric_base.MetricBase):
         self.feature_fn = feature_fn
         self._real_features = None
 
-    def _features(self, images, device):
-        f = self.feature_fn(images)
-        return torch.as_tensor(f).to(device, torch.float32)          # features stay on the device
-
     def _evaluate(self, Gs, Gs_kwargs, num_gpus):
         if self.feature_fn is None:
             raise RuntimeError('PR needs feature_fn: the reference\'s metrics/vgg16.pkl is not available in this tree')
-        if self._process_group is not None:
-            if self._real_features is None:
-                self._real_features = self._gather_shard_features(Gs, Gs_kwargs, 'real')
-            ref_features = self._real_features
-            eval_features = self._gather_shard_features(Gs, Gs_kwargs, 'fake')
-        else:
-            ref_features, eval_features = self._collect_features(Gs, Gs_kwargs, num_gpus)
+        if self._real_features is None:      # cached per object
+            self._real_features = self._feature_matrix(Gs, Gs_kwargs, 'real', num_gpus)
+        ref_features = self._real_features
+        eval_features = self._feature_matrix(Gs, Gs_kwargs, 'fake', num_gpus)
 
         # Precision and recall (the reference passes row_batch_size for both batch sizes, :219-220).
         state = knn_precision_recall_features(ref_features=ref_features, eval_features=eval_features, nhood_sizes=[self.nhood_size],
@@ -271,29 +264,3 @@ class PR(metric_base.MetricBase):
                                               process_group=self._process_group)
         self._report_result(state.knn_precision[0], suffix='_precision')
         self._report_result(state.knn_recall[0], suffix='_recall')
-
-    def _collect_features(self, Gs, Gs_kwargs, num_gpus):
-        """One process: the features of `num_images` reals (cached per object) and fakes."""
-        minibatch_size = num_gpus * self.minibatch_per_gpu
-
-        # Features of the reals, cached per object.
-        if self._real_features is None:
-            ref_features = None
-            for idx, images in enumerate(self._iterate_reals(minibatch_size=minibatch_size)):
-                begin = idx * minibatch_size
-                end = min(begin + minibatch_size, self.num_images)
-                f = self._features(torch.from_numpy(images[:end - begin]).to(Gs.device), Gs.device)
-                if ref_features is None:
-                    ref_features = torch.empty([self.num_images, f.shape[1]], device=Gs.device, dtype=torch.float32)
-                ref_features[begin:end] = f
-                if end == self.num_images:
-                    break
-            self._real_features = ref_features
-        ref_features = self._real_features
-
-        # Features of the fakes.
-        eval_features = torch.empty_like(ref_features)
-        for begin in range(0, self.num_images, minibatch_size):
-            end = min(begin + minibatch_size, self.num_images)
-            eval_features[begin:end] = self._features(self._generate(Gs, minibatch_size, Gs_kwargs), Gs.device)[:end - begin]
-        return ref_features, eval_features
