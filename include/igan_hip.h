@@ -46,7 +46,7 @@ extern "C" {
  * igan_moments_merge, igan_class_hist_update, igan_prob_stats_update, igan_nnk_update, igan_softmax_xent_fwd, igan_softmax_xent_bwd,
  * igan_xent_stats_update, igan_sigmoid_xent_fwd, igan_sigmoid_xent_bwd, igan_sigmoid_xent_stats_update, igan_binary_probs,
  * igan_filter_images_grouped (with struct igan_filter_image_desc, igan_struct_size id 9), igan_debug_filter_image_launches,
- * igan_manifold_member_nn1_update). */
+ * igan_manifold_member_nn1_update, igan_ball_count_update). */
 #define IGAN_ABI_VERSION 10
 
 typedef void* igan_stream_t; /* hipStream_t */
@@ -585,6 +585,29 @@ int igan_manifold_member_nn1_update(igan_stream_t stream, const float* query, co
                                     int* best_idx /* [nq], caller-initialised to INT32_MAX */,
                                     float* dots /* caller workspace, nq*nc floats */,
                                     int nq, int nc, int dim, int nk, int idx_base);
+
+/* igan_ball_count_update: how many candidates lie inside each QUERY's own balls -- the count behind density and coverage
+ * (Naeem et al., "Reliable Fidelity and Diversity Metrics for Generative Models", ICML 2020, the `prdc` definitions; the
+ * reference has no such metric).  For every query q and column s it ADDS to count[q][s] the number of candidates c of the
+ * batch with
+ *   d2(q, c) <  query_radius[q][s]     (inclusive = 0: prdc's strict comparison)
+ *   d2(q, c) <= query_radius[q][s]     (inclusive = 1: the comparison of igan_manifold_member_update)
+ * on the exact squared distance of the entries above: the fp32 MFMA product screens with the same error interval, a pair whose
+ * whole interval is on one side of the radius is decided by it, every other pair is measured as a direct difference in fp64.
+ * The radii belong to the queries (squared, fp64, typically igan_knn_radius_update's), not to the candidates.  No early exit,
+ * no atomic, no floating-point sum: count is a function of the multiset of (query, candidate) pairs fed, so candidate batches
+ * may be streamed in any order and cut anywhere, and a batch fed twice counts twice.  Initialise count to 0.  A pair whose
+ * exact distance is not finite is never counted and changes no other pair; a NaN or negative radius counts nothing; radius
+ * +infinity counts every candidate at a finite distance; an interval that is NaN (overflowed fp32 products or norms) decides
+ * nothing and the pair is measured.  Non-null buffers, the operand limits of igan_conv2d (an empty batch is refused),
+ * 1 <= nk <= 8, inclusive 0 or 1 (IGAN_ERR_INVALID_ARGUMENT), checked before anything touches a device.
+ */
+int igan_ball_count_update(igan_stream_t stream, const float* query, const float* qnorm,
+                           const double* query_radius /* [nq][nk] squared, fp64 */,
+                           const float* cand, const float* cnorm,
+                           long long* count /* [nq][nk], ADDED to */,
+                           float* dots /* caller workspace, nq*nc floats */,
+                           int nq, int nc, int dim, int nk, int inclusive /* 0: e < R, 1: e <= R */);
 
 /* ------------------------------------------------------------------------
  * One exact k-means step for the PRD metric (reference: precision-recall-distributions/prd_score.py:125-127, the

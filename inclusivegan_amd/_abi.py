@@ -214,6 +214,7 @@ SIGNATURES = {
     'igan_knn_radius_update': (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I]),
     'igan_manifold_member_update': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I]),
     'igan_manifold_member_nn1_update': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I]),
+    'igan_ball_count_update': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I]),
     'igan_kmeans_workspace_bytes': (_SZ, [_I, _I, _I]),
     'igan_kmeans_step': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I]),
     'igan_moments_workspace_bytes': (_SZ, [_I, _I]),

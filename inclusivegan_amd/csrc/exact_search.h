@@ -1,8 +1,8 @@
-// The procedure every exact search shares (exact_search.hip: 1-NN, k-NN with indices, k-th radius, manifold membership;
-// kmeans.hip: nearest centre), each piece defined once.  One wavefront owns a query.  The fp32 MFMA product only SCREENS:
+// The procedure every exact search shares (exact_search.hip: 1-NN, k-NN with indices, k-th radius, manifold membership, ball
+// count; kmeans.hip: nearest centre), each piece defined once.  One wavefront owns a query.  The fp32 MFMA product only SCREENS:
 // a = |q|^2 + |c|^2 - 2 q.c is trusted to the interval of nn1_tol (exact_distance.h), a candidate the interval cannot rule out is
 // a CONTENDER, every contender is measured by wave_sqdist in fp64 and the choice is made on exact values.  A mistake here is a
-// silently wrong neighbour in all five kernels.
+// silently wrong neighbour in all six kernels.
 #pragma once
 #include "exact_distance.h"
 
@@ -28,7 +28,7 @@ struct Screen {
 // NaN policy.  An fp32 product or norm that overflowed makes the interval NaN: it decides nothing.  Whether a candidate with
 // lower bound `lo` contends against the bound `u` is one of these two predicates, which differ for a NaN `lo` only:
 //   the 1-NN DROPS an undecidable candidate -- it is never measured and never wins, whatever its exact distance;
-//   the k-lists, the membership test and k-means MEASURE it -- it enters when its fp64 distance is finite.
+//   the k-lists, the membership test, the ball count and k-means MEASURE it -- it enters when its fp64 distance is finite.
 // So igan_nnk_update with k = 1 and igan_nn1_update agree while the screening values are not NaN (include/igan_hip.h).
 __device__ __forceinline__ bool contends_if_decided(double lo, double u) { return lo <= u; }
 __device__ __forceinline__ bool contends_unless_ruled_out(double lo, double u) { return !(lo > u); }

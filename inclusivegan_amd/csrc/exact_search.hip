@@ -12,6 +12,8 @@
 //               the reference estimates a manifold as one hypersphere per point, its radius the distance to the point's k-th
 //               neighbour (metrics/precision_recall.py:73-90: np.partition of a [10 000 x n] fp16 distance block on the
 //               host), and calls a sample "in" when it lies within the radius of any point (:119-120, `<=`).
+//   ball_count  no counterpart in the reference: density and coverage (Naeem et al., ICML 2020; the `prdc` package) count, per
+//               real, the fakes strictly inside the real's own k-NN ball (`<`, where pr50k3 has `<=`).
 // MI355X design: |q - c|^2 = |q|^2 + |c|^2 - 2 q.c, so a batch of candidates is one [nq x dim] x [dim x nc] product on the
 // exact-fp32 MFMA (distance_products(): the implicit-GEMM kernel of conv2d as a 1x1 conv, both operands in their natural
 // row-major [rows][dim] layout), followed by a fold with one wavefront per query.  The product only SCREENS; the procedure
@@ -24,6 +26,7 @@
 //   knn_radius_fold      the kcap smallest exact distances (a MULTISET of values: duplicates count, so the value at position k
 //                        is what np.partition leaves there)
 //   manifold_member_fold an any-within-radius reduction against per-candidate radii
+//   ball_count_fold      an integer count of the candidates within per-QUERY radii
 #include "igan_common.h"
 #include "exact_search.h"
 
@@ -267,6 +270,78 @@ __global__ __launch_bounds__(256) void manifold_member_fold_kernel(const float* 
     }
 }
 
+// The radius test of the ball count: strict (prdc's `<`) or inclusive (the `<=` of the membership test).
+template <bool INCLUSIVE>
+__device__ __forceinline__ bool within(double d, double R) { return INCLUSIVE ? d <= R : d < R; }
+
+// count[q][s] += #{c of the batch : d2(q, c) within R = query_radius[q][s]} -- the radii belong to the QUERIES, so R is
+// wave-uniform.  For a pair (q, c) and column s:
+//   a + t within R (and finite)  surely inside: counted in a lane-local integer, never measured;
+//   a - t beyond R               ruled out (strict: a - t >= R; inclusive: a - t > R);
+//   otherwise a contender: measured once for all of its open columns, counted in a wave-uniform integer when the exact
+//   distance is finite and within R.
+// The contender test is the NEGATION of "ruled out", so a NaN interval or a NaN radius falls through to measurement
+// (contends_unless_ruled_out) and the exact test then fails for a NaN.  There is no early exit -- every strip is screened --
+// no atomic and no floating-point sum: the state is a function of the multiset of (query, candidate) pairs fed.
+// The per-column counters sit under static indices (unrolled to 8, guarded by s < nk): registers, not scratch.
+template <bool INCLUSIVE>
+__global__ __launch_bounds__(256) void ball_count_fold_kernel(const float* __restrict__ dots, const float* __restrict__ qnorm,
+                                                              const float* __restrict__ cnorm, const float* __restrict__ query,
+                                                              const float* __restrict__ cand, const double* __restrict__ query_radius,
+                                                              long long* __restrict__ count, int nq, int nc, int dim, int nk) {
+    // q by readfirstlane: the compiler then knows the radii, the row pointers and the query's norm to be wave-uniform and keeps
+    // them in scalar registers (104 VGPRs without it, 4 waves per SIMD)
+    const int q = __builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
+    const int lane = threadIdx.x & 63;
+    if (q >= nq) return;
+    const double inf = (double)INFINITY;
+    double R[8];
+    int sure[8], measured[8];       // lane-local / wave-uniform; a batch has fewer than 2^31 candidates
+#pragma unroll
+    for (int s = 0; s < 8; s++) {
+        R[s] = (s < nk) ? query_radius[(size_t)q * nk + s] : 0.0;
+        sure[s] = 0;
+        measured[s] = 0;
+    }
+    const Screen screen{dots + (size_t)q * nc, cnorm, (double)qnorm[q], nn1_tol(dim)};
+    const float* qrow = query + (size_t)q * dim;
+    for (int c0 = 0; c0 < nc; c0 += 64) {
+        const int c = c0 + lane;
+        unsigned need = 0;
+        if (c < nc) {
+            const Interval iv = screen(c);
+#pragma unroll
+            for (int s = 0; s < 8; s++) {
+                if (s < nk) {
+                    const bool inside = iv.hi < inf && within<INCLUSIVE>(iv.hi, R[s]);
+                    const bool contends = INCLUSIVE ? contends_unless_ruled_out(iv.lo, R[s]) : !(iv.lo >= R[s]);
+                    sure[s] += inside ? 1 : 0;
+                    need |= (!inside && contends) ? 1u << s : 0u;
+                }
+            }
+        }
+        int j;
+        for (ContenderStrip strip(need != 0u); strip.next(j);) {
+            const unsigned todo = (unsigned)__shfl((int)need, j, 64);
+            const double e = wave_sqdist(qrow, cand + (size_t)(c0 + j) * dim, dim, lane);
+            if (e < inf) {                                     // false for NaN and +inf: never counted
+#pragma unroll
+                for (int s = 0; s < 8; s++)
+                    if (s < nk) measured[s] += (((todo >> s) & 1u) && within<INCLUSIVE>(e, R[s])) ? 1 : 0;
+            }
+        }
+    }
+#pragma unroll
+    for (int s = 0; s < 8; s++) {
+        if (s < nk) {
+            int n = sure[s];
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) n += __shfl_xor(n, off, 64);
+            if (lane == 0) count[(size_t)q * nk + s] += (long long)n + (long long)measured[s];
+        }
+    }
+}
+
 // What every search entry requires of a batch: the operand limits of igan_conv2d, which forms the products.
 int check_batch(const char* name, int nq, int nc, int dim) {
     if (!(nq >= 1 && nc >= 1 && dim >= 1)) return fail(IGAN_ERR_INVALID_ARGUMENT, "%s: sizes must be positive", name);
@@ -348,6 +423,24 @@ extern "C" int igan_manifold_member_update(igan_stream_t stream_, const float* q
     hipLaunchKernelGGL(manifold_member_fold_kernel, dim3(ceil_div(nq, 4)), dim3(256), 0, (hipStream_t)stream_, dots, qnorm, cnorm,
                        query, cand, cand_radius, member, nq, nc, dim, nk);
     IGAN_LAUNCH_CHECK("manifold_member_fold launch");
+    return IGAN_OK;
+}
+
+extern "C" int igan_ball_count_update(igan_stream_t stream_, const float* query, const float* qnorm, const double* query_radius,
+                                      const float* cand, const float* cnorm, long long* count, float* dots,
+                                      int nq, int nc, int dim, int nk, int inclusive) {
+    IGAN_REQUIRE(query && qnorm && query_radius && cand && cnorm && count && dots, "ball_count_update: null buffer");
+    if (int rc = check_batch("ball_count_update", nq, nc, dim)) return rc;
+    IGAN_REQUIRE(nk >= 1 && nk <= 8, "ball_count_update: nk must be in [1, 8]");
+    IGAN_REQUIRE(inclusive == 0 || inclusive == 1, "ball_count_update: inclusive must be 0 (d2 < R) or 1 (d2 <= R)");
+    if (int rc = distance_products(stream_, query, cand, dots, nq, nc, dim)) return rc;
+    if (inclusive)
+        hipLaunchKernelGGL(ball_count_fold_kernel<true>, dim3(ceil_div(nq, 4)), dim3(256), 0, (hipStream_t)stream_, dots, qnorm, cnorm,
+                           query, cand, query_radius, count, nq, nc, dim, nk);
+    else
+        hipLaunchKernelGGL(ball_count_fold_kernel<false>, dim3(ceil_div(nq, 4)), dim3(256), 0, (hipStream_t)stream_, dots, qnorm, cnorm,
+                           query, cand, query_radius, count, nq, nc, dim, nk);
+    IGAN_LAUNCH_CHECK("ball_count_fold launch");
     return IGAN_OK;
 }
 

@@ -2417,6 +2417,29 @@ def manifold_member_nn1_update_raw(query, qnorm, cand, cnorm, cand_radius, membe
                                                    _ptr(member), _ptr(best_d2), _ptr(best_idx), _ptr(dots), nq, nc, dim, nk, idx_base))
 
 
+def ball_count_state(nq, nk, device):
+    """Running state of igan_ball_count_update for nq queries and nk radii each: int64 [nq, nk] = 0."""
+    if not 1 <= int(nk) <= 8:
+        raise ValueError('ball_count_state: nk must be in [1, 8]')
+    return torch.zeros((nq, int(nk)), device=device, dtype=torch.int64)
+
+
+def ball_count_update_raw(query, qnorm, query_radius, cand, cnorm, count, inclusive=False):
+    """Add to count[q, s] (int64 [nq, nk], contiguous view, starts at 0) the number of candidates of the batch whose exact squared
+    distance to query q is < query_radius[q, s] (fp64 [nq, nk]; `inclusive`: <=).  No early exit: a batch fed twice counts twice."""
+    lib = _abi.get_plugin()
+    query, qnorm, cand, cnorm, dots = _search_operands('ball_count_update', query, qnorm, cand, cnorm)
+    (nq, dim), nc = query.shape, cand.shape[0]
+    if query_radius.dtype != torch.float64 or query_radius.dim() != 2 or not query_radius.is_cuda:
+        raise TypeError('ball_count_update: query_radius must be a device float64 [nq, nk]')
+    _search_state('ball_count_update', 'count', count, torch.int64, nq)
+    query_radius, nk = query_radius.contiguous(), count.shape[1]
+    if tuple(query_radius.shape) != (nq, nk):
+        raise ValueError('ball_count_update: shapes of query, query_radius and count do not agree')
+    _abi.check(lib.igan_ball_count_update(_stream(), _ptr(query), _ptr(qnorm), _ptr(query_radius), _ptr(cand), _ptr(cnorm),
+                                          _ptr(count), _ptr(dots), nq, nc, dim, nk, 1 if inclusive else 0))
+
+
 # ---- exact k-means step (csrc/kmeans.hip; the PRD metric) -------------------------------------------------------------------
 KMEANS_MAX_CLUSTERS = 64
 KMEANS_MAX_DIM = 4096

@@ -89,6 +89,14 @@ def _gather_search_rows(own, n, group):
     return metric_base.gather_rows(out, [[search_rows(n, r, world)] for r in range(world)], own, group)
 
 
+def clamp_batch_sizes(dim, row_batch_size, col_batch_size):
+    """(row, col) batch sizes a search pass can use: the kernels address an operand through 32-bit byte offsets (below 2 GiB each,
+    like DCI.query_chunk / cand_chunk), and the product block of one pass through an int32 element count."""
+    fit = max(1, 0x7FFFFFF0 // (4 * max(dim, 1)) - 1)
+    row_batch_size = max(1, min(int(row_batch_size), fit))
+    return row_batch_size, max(1, min(int(col_batch_size), fit, _INT32_MAX // row_batch_size))
+
+
 class ManifoldEstimator():
     """Estimate of the manifold of given feature vectors (reference :61-134): one squared radius per point and neighbourhood
     size.  `distance_block` is accepted for the reference's signature and not used (None is fine)."""
@@ -107,11 +115,7 @@ class ManifoldEstimator():
             raise ValueError('ManifoldEstimator: %d points cannot have a neighbour at position %d' % (num_images, max(self.nhood_sizes)))
         if max(self.nhood_sizes) + 1 > 16 or self.num_nhoods > 8:
             raise ValueError('ManifoldEstimator: the HIP search keeps at most 16 distances per point (nhood sizes <= 15) and 8 neighbourhood sizes')
-        # The kernels address an operand through 32-bit byte offsets (below 2 GiB each, like DCI.query_chunk / cand_chunk), and the
-        # product block of one pass through an int32 element count.
-        fit = max(1, 0x7FFFFFF0 // (4 * max(dim, 1)) - 1)
-        self.row_batch_size = max(1, min(int(row_batch_size), fit))
-        self.col_batch_size = max(1, min(int(col_batch_size), fit, _INT32_MAX // self.row_batch_size))
+        self.row_batch_size, self.col_batch_size = clamp_batch_sizes(dim, row_batch_size, col_batch_size)
         self._ref_norms = hip_ops.row_sqnorm_raw(self._ref_features)
 
         # Squared distance to the k-th neighbour of every point: the kcap = max(nhood) + 1 smallest of its row.
