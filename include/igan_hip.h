@@ -46,7 +46,7 @@ extern "C" {
  * igan_moments_merge, igan_class_hist_update, igan_prob_stats_update, igan_nnk_update, igan_softmax_xent_fwd, igan_softmax_xent_bwd,
  * igan_xent_stats_update, igan_sigmoid_xent_fwd, igan_sigmoid_xent_bwd, igan_sigmoid_xent_stats_update, igan_binary_probs,
  * igan_filter_images_grouped (with struct igan_filter_image_desc, igan_struct_size id 9), igan_debug_filter_image_launches,
- * igan_manifold_member_nn1_update, igan_ball_count_update). */
+ * igan_manifold_member_nn1_update, igan_ball_count_update, igan_poly3_kernel_sums_workspace_bytes, igan_poly3_kernel_sums). */
 #define IGAN_ABI_VERSION 10
 
 typedef void* igan_stream_t; /* hipStream_t */
@@ -672,6 +672,34 @@ int igan_moments_finalize(igan_stream_t stream, const double* sum, const double*
                           double* mean /* [F] */, double* cov /* [F][F] */, long long n_total, int F);
 int igan_moments_merge(igan_stream_t stream, double* sum_a, double* gram_a, const double* shift_a /* [F] or NULL = 0 */,
                        const double* sum_b, const double* gram_b, const double* shift_b /* [F] or NULL = 0 */, long long n_b, int F);
+
+/* ------------------------------------------------------------------------
+ * Pair sums of the cubic polynomial kernel for the Kernel Inception Distance (kid50k; Binkowski et al., "Demystifying MMD
+ * GANs", ICLR 2018; the reference has no such metric).  Two more exports under version 10.  With
+ *   k(a, b) = (gamma * a.b + coef0)^3,   x_i = X[idx_x[s][i]],   y_j = Y[idx_y[s][j]]   (i, j positions in [0, m))
+ * igan_poly3_kernel_sums OVERWRITES, for every subset s of the S subsets,
+ *   out[s][0] = sum over i != j of k(x_i, x_j)     out[s][1] = sum over i != j of k(y_i, y_j)     out[s][2] = sum over all i, j of k(x_i, y_j)
+ * The diagonal that the two symmetric sums skip (it is skipped, not subtracted) is the diagonal of POSITIONS: a subset that
+ * lists one row twice at two positions counts that pair.  X and Y may be the same matrix.
+ * Arithmetic: every fp32 feature is widened to fp64 before any product, the dot products accumulate in fp64 on
+ * v_mfma_f64_16x16x4_f64 four features per instruction, the instructions in ascending feature order, v = fma(gamma, dot, coef0) and (v * v) * v are fp64; no fp32 value is
+ * formed after the load.  Rows are gathered by index while they are staged; no copy of a subset exists.  One workgroup owns a
+ * 64 x 64 tile of one pair matrix of one subset (tiles on or above the diagonal for the symmetric sums, a tile strictly above
+ * it counted twice), adds its cells in a fixed order -- lane-local, the xor tree of a wavefront, the four wavefronts in order
+ * -- into ONE fp64 of `partials`, and a second kernel adds the partials of a (subset, sum) serially in tile order: no atomic,
+ * no split over F.  out[s] is a function of subset s's indices and features only: the same bits launched alone or among
+ * others, on every run, whatever `partials` held.  A NaN or infinity in a row reaches only the sums of the subsets that list
+ * that row (sums 0 and 2 for a row of X, 1 and 2 for a row of Y); a subset that does not list it is bit-identical.
+ * INDICES ARE NOT RANGE-CHECKED on the device: the caller owns 0 <= idx_x < nx and 0 <= idx_y < ny (the Python binding checks
+ * on the host before it uploads); nx and ny are validated as sizes only.
+ * Limits: 1 <= F <= 4096 and S * m and S * (2 T^2 + T) tiles, T = ceil(m / 64), below 2^31 (IGAN_ERR_UNSUPPORTED beyond);
+ * S >= 1, m >= 2, nx >= 1, ny >= 1, non-null buffers, X / Y / idx_* 4-byte and partials / out 8-byte aligned
+ * (IGAN_ERR_INVALID_ARGUMENT), all checked before a launch.  partials: igan_poly3_kernel_sums_workspace_bytes(S, m) bytes
+ * (0 for sizes outside the limits), contents irrelevant before and after. */
+size_t igan_poly3_kernel_sums_workspace_bytes(int S, int m);
+int igan_poly3_kernel_sums(igan_stream_t stream, const float* X /* [nx][F] row-major */, int nx, const float* Y /* [ny][F] */, int ny,
+                           const int* idx_x /* [S][m] rows of X */, const int* idx_y /* [S][m] rows of Y */, int S, int m, int F,
+                           double gamma, double coef0, double* partials /* workspace */, double* out /* [S][3] */);
 
 /* ------------------------------------------------------------------------
  * Per-class statistics of classifier outputs, folded batch by batch on the device.  Added without a version bump: two more

@@ -219,6 +219,8 @@ SIGNATURES = {
     'igan_kmeans_step': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I]),
     'igan_moments_workspace_bytes': (_SZ, [_I, _I]),
     'igan_moments_update': (_I, [_P, _P, _P, _P, _P, _P, _SZ, _I, _I]),
+    'igan_poly3_kernel_sums_workspace_bytes': (_SZ, [_I, _I]),
+    'igan_poly3_kernel_sums': (_I, [_P, _P, _I, _P, _I, _P, _P, _I, _I, _I, ctypes.c_double, ctypes.c_double, _P, _P]),
     'igan_moments_finalize': (_I, [_P, _P, _P, _P, _P, _P, _LL, _I]),
     'igan_moments_merge': (_I, [_P, _P, _P, _P, _P, _P, _P, _LL, _I]),
     'igan_class_hist_update': (_I, [_P, _P, _P, _P, _I, _I]),

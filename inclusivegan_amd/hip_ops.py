@@ -2555,6 +2555,58 @@ def moments_merge_raw(sum_a, gram_a, shift_a, sum_b, gram_b, shift_b, n_b):
     _abi.check(lib.igan_moments_merge(_stream(), _ptr(sum_a), _ptr(gram_a), _ptr(shift_a), _ptr(sum_b), _ptr(gram_b), _ptr(shift_b), int(n_b), F))
 
 
+# ---- pair sums of the cubic polynomial kernel (csrc/poly_kernel_sum.hip; the KID metric) -------------------------------------
+def _host_row_numbers(name, what, idx, rows):
+    """Host integer array [S, m] of row numbers in [0, rows) -> contiguous int32 copy; anything else raises before a device is touched."""
+    if torch.is_tensor(idx):
+        raise TypeError('%s: %s must be a host (NumPy) integer array [S, m], not a tensor' % (name, what))
+    idx = np.asarray(idx)
+    if idx.ndim != 2 or not np.issubdtype(idx.dtype, np.integer):
+        raise ValueError('%s: %s must be an integer array [S, m] (got %s %s)' % (name, what, idx.dtype, idx.shape))
+    if idx.size and (int(idx.min()) < 0 or int(idx.max()) >= rows):
+        raise ValueError('%s: %s holds row numbers outside [0, %d) (min %d, max %d)' % (name, what, rows, int(idx.min()), int(idx.max())))
+    return np.ascontiguousarray(idx, dtype=np.int32)
+
+
+def poly3_kernel_sums(X, Y, idx_x, idx_y, gamma, coef0, workspace=None):
+    """The three pair sums of k(a, b) = (gamma a.b + coef0)^3 over S subsets of m gathered rows (igan_poly3_kernel_sums) ->
+    float64 [S, 3] on the device: [s, 0] = sum over positions i != j of k(x_i, x_j), [s, 1] the same over y, [s, 2] = sum over
+    all i, j of k(x_i, y_j), with x_i = X[idx_x[s, i]], y_j = Y[idx_y[s, j]].  X [nx, F], Y [ny, F]: contiguous fp32 device tensors
+    (the same tensor is allowed); idx_x, idx_y: HOST integer arrays [S, m], range-checked here (ValueError) and uploaded as int32,
+    so nothing out of range reaches the kernel, which does not check.  fp64 on the f64 matrix instruction, fixed order: row s
+    depends on subset s alone and has the same bits on every run.  One launch for all S subsets, no synchronisation.
+    `workspace`: an optional contiguous float64 device tensor of at least the queried size, contents irrelevant."""
+    if X.dim() != 2 or Y.dim() != 2 or X.shape[1] != Y.shape[1]:
+        raise ValueError('poly3_kernel_sums: X must be [nx, F] and Y [ny, F] with one F (got %s, %s)' % (tuple(X.shape), tuple(Y.shape)))
+    (nx, F), ny = (int(v) for v in X.shape), int(Y.shape[0])
+    ix = _host_row_numbers('poly3_kernel_sums', 'idx_x', idx_x, nx)
+    iy = _host_row_numbers('poly3_kernel_sums', 'idx_y', idx_y, ny)
+    if ix.shape != iy.shape:
+        raise ValueError('poly3_kernel_sums: idx_x and idx_y must have one shape [S, m] (got %s, %s)' % (ix.shape, iy.shape))
+    S, m = ix.shape
+    _require_cuda_f32(X, Y)
+    if not X.is_contiguous() or not Y.is_contiguous() or X.device != Y.device:
+        raise ValueError('poly3_kernel_sums: X and Y must be contiguous and on one device')
+    lib = _abi.get_plugin()
+    nbytes = int(lib.igan_poly3_kernel_sums_workspace_bytes(S, m)) if 1 <= F <= MOMENTS_MAX_F else 0
+    if nbytes == 0:
+        raise NotImplementedError('poly3_kernel_sums: S >= 1, m >= 2, 1 <= F <= %d and S * m and the tile count below 2^31 '
+                                  '(got S %d, m %d, F %d)' % (MOMENTS_MAX_F, S, m, F))
+    dev = X.device
+    if workspace is None:
+        partials = torch.empty(nbytes // 8, device=dev, dtype=torch.float64)
+    else:
+        _require_cuda_f64('poly3_kernel_sums', workspace)
+        if workspace.numel() * 8 < nbytes or workspace.device != dev:
+            raise ValueError('poly3_kernel_sums: the workspace needs %d bytes on %s' % (nbytes, dev))
+        partials = workspace
+    out = torch.empty((S, 3), device=dev, dtype=torch.float64)
+    ix_d, iy_d = torch.from_numpy(ix).to(dev), torch.from_numpy(iy).to(dev)
+    _abi.check(lib.igan_poly3_kernel_sums(_stream(), _ptr(X), nx, _ptr(Y), ny, _ptr(ix_d), _ptr(iy_d), S, m, F, float(gamma), float(coef0),
+                                          _ptr(partials), _ptr(out)))
+    return out
+
+
 class FeatureMoments:
     """Mean and covariance of a stream of feature batches, kept on the device (np.mean / np.cov(rowvar=False) of the rows seen).
 
