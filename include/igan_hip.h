@@ -46,7 +46,8 @@ extern "C" {
  * igan_moments_merge, igan_class_hist_update, igan_prob_stats_update, igan_nnk_update, igan_softmax_xent_fwd, igan_softmax_xent_bwd,
  * igan_xent_stats_update, igan_sigmoid_xent_fwd, igan_sigmoid_xent_bwd, igan_sigmoid_xent_stats_update, igan_binary_probs,
  * igan_filter_images_grouped (with struct igan_filter_image_desc, igan_struct_size id 9), igan_debug_filter_image_launches,
- * igan_manifold_member_nn1_update, igan_ball_count_update, igan_poly3_kernel_sums_workspace_bytes, igan_poly3_kernel_sums). */
+ * igan_manifold_member_nn1_update, igan_ball_count_update, igan_poly3_kernel_sums_workspace_bytes, igan_poly3_kernel_sums);
+ * likewise, for the differentiable augmentation of D's inputs: igan_diffaugment_workspace_bytes, igan_diffaugment_fwd, igan_diffaugment_bwd. */
 #define IGAN_ABI_VERSION 10
 
 typedef void* igan_stream_t; /* hipStream_t */
@@ -891,6 +892,38 @@ int igan_images_to_uint8(igan_stream_t stream, const float* x, unsigned char* y,
                          long long stride_n, long long stride_c, long long stride_h, long long stride_w);
 int igan_images_from_uint8(igan_stream_t stream, const unsigned char* x, float* y, int N, int C, int H, int W,
                            float scale, float bias, int nhwc_in);
+
+/* ------------------------------------------------------------------------
+ * Differentiable augmentation of the images D sees, reals and fakes (Zhao et al., "Differentiable Augmentation for Data-Efficient
+ * GAN Training", NeurIPS 2020; the reference has no such step: training/augment.py, training/loss.py `augment=`).  Three more exports
+ * under version 10, no struct.  Arguments are validated before anything touches a device.
+ *
+ * x, y: [n][h][w][c] fp32, 1 <= c <= 4.  u: [n][8] fp32 uniforms in [0, 1), one row per sample (column 7 is padding).  policy is a bit
+ * set, 1 = color, 2 = translation, 4 = cutout, always applied in that order.  Integer parameters are derived on the device as
+ *     draw(u, k) = min(floor(fl32(u * k)), k - 1)          the product rounded to fp32 (the clamp holds it below k whatever that rounding does)
+ *   color        b = u0 - 1/2, s = 2 u1, c = u2 + 1/2;  m = mean of the sample's c h w inputs, summed in fp64 in a fixed order
+ *                (csrc/diffaugment.hip states it) and rounded to fp32 once;  M = m + b;  per pixel xb_k = x_k + b, p = mean_k xb_k,
+ *                    v_k = ((xb_k - p) s + p - M) c + M        (brightness, saturation, contrast; fp32, one rounding per operation)
+ *   translation  S_y = floor(h / 8 + 1/2), t_y = draw(u4, 2 S_y + 1) - S_y; t_x likewise from u3 and w;
+ *                    w(i, j) = v(i + t_y, j + t_x) where that lies inside the image, else exactly 0  (m is that of the untranslated image)
+ *   cutout       K_y = floor(h / 2 + 1/2), r_y = 1 - K_y mod 2, o_y = draw(u6, h + r_y): rows o_y - K_y / 2 <= i < o_y - K_y / 2 + K_y
+ *                are cut; columns likewise from u5 and w; a pixel whose row and column are both cut is exactly 0.
+ * igan_diffaugment_bwd is the transpose: g(i, j) = dy(i - t_y, j - t_x) where that position is inside the image and not cut, else 0;
+ * without color dx = g; with color Gm = mean of g over the sample (fp64 sum, rounded once), q = mean_k g_k,
+ *     dx_k = (c s) g_k + (c (1 - s)) q + (1 - c) Gm.
+ * A cut or shifted-out value is 0 whatever its source holds; without color kept values are bit copies (policy 0: a plain copy).  With
+ * color a non-finite input makes every kept value of its own sample non-finite and touches no other sample.
+ * Launches: one, or with color two (one reduction, one pass).  No allocation, no host read, no atomic: capturable, and the same inputs
+ * give the same bits whatever n and the sample's place in the batch.
+ * workspace: igan_diffaugment_workspace_bytes(n, c, h, w) bytes, 8-byte aligned, contents irrelevant; needed with color only (may be
+ * NULL otherwise).  The size is 0 exactly for the shapes the entry points refuse with IGAN_ERR_UNSUPPORTED: c > 4, or n * c * h * w
+ * at or beyond 2^31.  IGAN_ERR_INVALID_ARGUMENT: a null buffer, n, c, h or w < 1, unknown policy bits, y == x, x / y not aligned to
+ * the pixel access (16 bytes for c = 4, 8 for c = 2, else 4). */
+size_t igan_diffaugment_workspace_bytes(int n, int c, int h, int w);
+int igan_diffaugment_fwd(igan_stream_t stream, const float* x, float* y, const float* u /* [n][8] */, int n, int c, int h, int w,
+                         int policy, void* workspace);
+int igan_diffaugment_bwd(igan_stream_t stream, const float* dy, float* dx, const float* u /* [n][8] */, int n, int c, int h, int w,
+                         int policy, void* workspace);
 
 /* ------------------------------------------------------------------------
  * Device-side time stamps (measurement support, not part of the reference's surface): igan_stamp writes the constant

@@ -241,6 +241,9 @@ SIGNATURES = {
     'igan_linear_svc_predict': (_I, [_P, _P, _P, _I, _I]),
     'igan_images_to_uint8': (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _F, _F, _I, _LL, _LL, _LL, _LL]),
     'igan_images_from_uint8': (_I, [_P, _P, _P, _I, _I, _I, _I, _F, _F, _I]),
+    'igan_diffaugment_workspace_bytes': (_SZ, [_I, _I, _I, _I]),
+    'igan_diffaugment_fwd': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    'igan_diffaugment_bwd': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     'igan_stamp': (_I, [_P, _P]),
     'igan_debug_set_conv_diag': (None, [_P]),
     'igan_stamp_accumulate': (_I, [_P, _P, _P, _I, _I]),

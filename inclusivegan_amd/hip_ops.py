@@ -3275,6 +3275,70 @@ def images_from_uint8(images, drange=(-1, 1), nhwc_to_nchw=False):
     return out
 
 
+# ---- differentiable augmentation of D's inputs (csrc/diffaugment.hip; training/augment.py states the transform) ----------------
+DIFFAUGMENT_COLOR, DIFFAUGMENT_TRANSLATION, DIFFAUGMENT_CUTOUT = 1, 2, 4
+DIFFAUGMENT_MAX_CHANNELS = 4
+
+
+def diffaugment_raw(x, u, policy_bits, transpose=False):
+    """The transform (or, with `transpose`, its exact transpose applied to a gradient) of x [n, C, H, W] fp32 under the policy bit set
+    (1 color, 2 translation, 4 cutout) with one row of u [n, 8] fp32 uniforms per sample: one launch, two with color.  Returns a new
+    channels_last tensor.  No autograd, no host synchronisation."""
+    lib = _abi.get_plugin()
+    _require_cuda_f32(x, u)
+    bits = int(policy_bits)
+    if bits < 1 or bits > 7:
+        raise ValueError('diffaugment: policy bits must be a non-empty subset of 1 | 2 | 4 (got %d); an empty policy is not a call' % bits)
+    if x.dim() != 4 or tuple(u.shape) != (int(x.shape[0]), 8):
+        raise ValueError('diffaugment: x must be [n, C, H, W] and u [n, 8] (got %s and %s)' % (tuple(x.shape), tuple(u.shape)))
+    x = nhwc(x)
+    u = u.contiguous()
+    n, c, h, w = (int(v) for v in x.shape)
+    ws_bytes = int(lib.igan_diffaugment_workspace_bytes(n, c, h, w))
+    if ws_bytes == 0:
+        raise NotImplementedError('diffaugment: n >= 1, 1 <= C <= %d and n * C * H * W below 2^31 (got %s)' % (DIFFAUGMENT_MAX_CHANNELS, tuple(x.shape)))
+    ws = torch.empty((ws_bytes // 8,), device=x.device, dtype=torch.float64) if bits & DIFFAUGMENT_COLOR else None
+    y = empty_nchw(n, c, h, w, x)
+    fn = lib.igan_diffaugment_bwd if transpose else lib.igan_diffaugment_fwd
+    _abi.check(fn(_stream(), _ptr(x), _ptr(y), _ptr(u), n, c, h, w, bits, _ptr(ws)))
+    return y
+
+
+class _DiffAugmentGradFn(torch.autograd.Function):
+    """The transpose kernel as a node of its own, so that differentiating it again is an error and not a silent zero."""
+
+    @staticmethod
+    def forward(ctx, dy, u, bits):
+        return diffaugment_raw(dy, u, bits, transpose=True)
+
+    @staticmethod
+    def backward(ctx, g):
+        raise NotImplementedError('diffaugment: second-order gradients are not built (R1 is taken with respect to the AUGMENTED reals, so no '
+                                  'training op differentiates the transform twice: DESIGN.md)')
+
+
+class DiffAugmentFn(torch.autograd.Function):
+    """y = T_u(x) for x [n, C, H, W] fp32 (dense NCHW is converted to channels_last), u [n, 8] fp32 uniforms, policy bits.  Linear in
+    x apart from the colour mean, which the transpose carries too; only x is differentiated."""
+
+    @staticmethod
+    def forward(ctx, x, u, policy_bits):
+        ctx.save_for_backward(u)
+        ctx.bits = int(policy_bits)
+        return diffaugment_raw(x, u, ctx.bits)
+
+    @staticmethod
+    def backward(ctx, dy):
+        (u,) = ctx.saved_tensors
+        if torch.is_grad_enabled():
+            return _DiffAugmentGradFn.apply(dy, u, ctx.bits), None, None
+        return diffaugment_raw(dy, u, ctx.bits, transpose=True), None, None
+
+
+def diffaugment(x, u, policy_bits):
+    return DiffAugmentFn.apply(x, u, policy_bits)
+
+
 # ----------------------------------------------------------------------------
 # optimizer
 

@@ -26,7 +26,10 @@ from .metrics.metric_defaults import metric_defaults      # the metrics built he
 def build_kwargs(dataset, data_dir, result_dir, config_id, num_gpus, gamma, mirror_augment, metrics, resume_pkl,
                  minibatch_gpu, data_size, num_epochs, init_proj_dim, init_staleness, num_samples_factor, knn_perturb_factor,
                  candidate_batch_size, exclusive_retrieved_code, NN_rec_lpips_weight, dist_thres_percentile, attr_interesting,
-                 init_mul):
+                 init_mul, diffaugment=None):
+    """`diffaugment`: None, or a policy such as 'color,translation,cutout' (training/augment.py) -- the one argument the reference
+    does not have.  With None the result is exactly the reference's; with a policy both loss dictionaries gain `augment` and the
+    run description `_aug_<names>`.  The policy is not network state: pickles, resume and the metrics do not know about it."""
     assert config_id in _valid_configs
     if config_id in ('config-a', 'config-b', 'config-c', 'config-d'):
         raise NotImplementedError('configs a-d (progressive growing / StyleGAN-1 nets) are outside the hot path; '
@@ -62,6 +65,11 @@ def build_kwargs(dataset, data_dir, result_dir, config_id, num_gpus, gamma, mirr
         init_staleness, num_samples_factor, knn_perturb_factor, NN_rec_lpips_weight)
     if attr_interesting is not None:
         desc += '_%s' % attr_interesting.replace(',', '_and_')
+    if diffaugment:
+        from .training import augment
+        names = augment.policy_names(augment.parse_policy(diffaugment))      # ValueError on an unknown name; the order of application
+        G_loss.augment = D_loss.augment = ','.join(names)
+        desc += '_aug_' + '_'.join(names)
     desc += '_scratch' if (resume_pkl is None or '_scratch' in resume_pkl) else '_finetune'
 
     train = EasyDict(
@@ -150,6 +158,7 @@ def main():
     p.add_argument('--dist-thres-percentile', default=100.0, type=float)
     p.add_argument('--attr-interesting', default=None, type=str)
     p.add_argument('--resume-pkl', default=None, type=str)
+    p.add_argument('--diffaugment', default=None, type=str, metavar='POLICY', help='differentiable augmentation of everything D sees: comma-separated subset of color,translation,cutout')
     p.add_argument('--attr-file', default=None, type=str, help='CelebA Anno/list_attr_celeba.txt (attribute vocabulary for --attr-interesting)')
     args = p.parse_args()
     if args.config_id not in _valid_configs:

@@ -8,6 +8,11 @@ evaluates everything like the reference graph; 'loss' / 'reg' return `None` for 
 
 Random draws (interp factors :36, latents :46,59,98, path-length noise :64) go through
 tflib.tfutil's injectable source.
+
+Both functions also take `augment` (None, or a policy such as 'color,translation,cutout': training/augment.py): differentiable
+augmentation of everything D sees.  With None no draw is made and no kernel is launched.  With a policy each phase makes ONE more
+uniform draw -- G's adversarial phase [B, 8] after its other draws; D's 'loss' / 'both' phases [fakes + reals, 8] right after the
+latents; D's 'reg' phase [B, 8] -- and R1 is taken with respect to the augmented reals.
 """
 import numpy as np
 import torch
@@ -18,6 +23,7 @@ from ..dnnlib.tflib import tfutil
 from ..dnnlib.tflib.autosummary import autosummary
 from .. import hip_ops
 from ..metrics import lpips as lpips_mod
+from . import augment as augment_mod
 
 #----------------------------------------------------------------------------
 
@@ -26,13 +32,13 @@ def _lpips_pair(lpips, a, b):
 
 def G_logistic_ns_rec_interp_arb_pathreg(G, D, lpips, training_set, minibatch_size, reals_rec_1, labels_rec_1, latents_rec_1, reals_rec_2, labels_rec_2, latents_rec_2,
     NN_rec_lpips_weight,
-    pl_minibatch_shrink=2, pl_decay=0.01, pl_weight=2.0, phase='both'):
+    pl_minibatch_shrink=2, pl_decay=0.01, pl_weight=2.0, phase='both', augment=None):
     with G.derived_scope(), D.derived_scope():     # weights are constant inside one loss evaluation
         return _G_loss_impl(G, D, lpips, training_set, minibatch_size, reals_rec_1, labels_rec_1, latents_rec_1, reals_rec_2, labels_rec_2,
-                            latents_rec_2, NN_rec_lpips_weight, pl_minibatch_shrink, pl_decay, pl_weight, phase)
+                            latents_rec_2, NN_rec_lpips_weight, pl_minibatch_shrink, pl_decay, pl_weight, phase, augment_mod.parse_policy(augment))
 
 def _G_loss_impl(G, D, lpips, training_set, minibatch_size, reals_rec_1, labels_rec_1, latents_rec_1, reals_rec_2, labels_rec_2, latents_rec_2,
-    NN_rec_lpips_weight, pl_minibatch_shrink, pl_decay, pl_weight, phase):
+    NN_rec_lpips_weight, pl_minibatch_shrink, pl_decay, pl_weight, phase, augment_bits=0):
     assert phase in ('both', 'loss', 'reg')
     dev = latents_rec_1.device
     latent_shape = G.input_shapes[0][1:]
@@ -79,8 +85,9 @@ def _G_loss_impl(G, D, lpips, training_set, minibatch_size, reals_rec_1, labels_
             labels_random = training_set.get_random_labels_tf(minibatch_size)
             arb_images_out = G.get_output_for(latents_random, labels_random, is_training=True)
 
-        # loss.py:49-52
-        arb_scores_out, _ = D.get_output_for(arb_images_out, labels_random, is_training=True)
+        # loss.py:49-52; with an augmentation policy D scores T(G(z)) and the gradient reaches G through T's transpose (the draw is the
+        # last of this phase; the LPIPS terms above and the path-length term below see un-augmented images)
+        arb_scores_out, _ = D.get_output_for(augment_mod.DiffAugment(arb_images_out, augment_bits), labels_random, is_training=True)
         loss_G_arb = F.softplus(-arb_scores_out)
         loss_G_arb = autosummary('Loss/loss_G_arb', loss_G_arb)
         loss = loss_addup(loss, loss_G_arb)
@@ -113,11 +120,11 @@ def _G_loss_impl(G, D, lpips, training_set, minibatch_size, reals_rec_1, labels_
     return loss, reg
 
 def D_logistic_r1(G, D, training_set, minibatch_size, reals, labels,
-    gamma=10.0, phase='both'):
+    gamma=10.0, phase='both', augment=None):
     with G.derived_scope(), D.derived_scope():
-        return _D_loss_impl(G, D, training_set, minibatch_size, reals, labels, gamma, phase)
+        return _D_loss_impl(G, D, training_set, minibatch_size, reals, labels, gamma, phase, augment_mod.parse_policy(augment))
 
-def _D_loss_impl(G, D, training_set, minibatch_size, reals, labels, gamma, phase):
+def _D_loss_impl(G, D, training_set, minibatch_size, reals, labels, gamma, phase, augment_bits=0):
     assert phase in ('both', 'loss', 'reg')
     dev = reals.device
     latent_shape = G.input_shapes[0][1:]
@@ -125,15 +132,25 @@ def _D_loss_impl(G, D, training_set, minibatch_size, reals, labels, gamma, phase
     reg = None
 
     need_reg = phase in ('both', 'reg')
-    if need_reg:
-        reals = reals.detach().requires_grad_(True)
+    # R1 (loss.py:107-111) is taken with respect to the AUGMENTED reals: the leaf is made after the augmentation, so the transform is
+    # never differentiated twice
+    if phase == 'reg':
+        reals = augment_mod.DiffAugment(reals, augment_bits).detach().requires_grad_(True)       # one draw [B, 8]
 
     if phase in ('both', 'loss'):
         # loss.py:98-105
         latents_random = tfutil.random_normal([minibatch_size * 2] + latent_shape, dev)
+        # ONE draw for both minibatches, right after the latents: rows 0 .. B-1 augment the fakes, rows B .. 2B-1 the reals, whichever
+        # branch evaluates D below (the augmentation comes before the interleave)
+        aug_u = tfutil.random_uniform([minibatch_size * 2 + int(reals.shape[0]), 8], dev) if augment_bits else None
         labels_random = training_set.get_random_labels_tf(minibatch_size * 2)
         with torch.no_grad():   # only D's trainables are differentiated in this step (training_loop.py:291)
             arb_images_out = G.get_output_for(latents_random, labels_random, is_training=True)
+            if augment_bits:
+                arb_images_out = augment_mod.augment(arb_images_out, aug_u[:minibatch_size * 2], augment_bits)
+                reals = augment_mod.augment(reals, aug_u[minibatch_size * 2:], augment_bits)      # once: serves the loss and, in 'both', R1
+        if need_reg:
+            reals = reals.detach().requires_grad_(True)
         gs = D.static_kwargs.get('mbstd_group_size', 6)
         if phase == 'loss' and arb_images_out.shape == reals.shape and (gs <= 1 or int(reals.shape[0]) % gs == 0):
             # D(fakes) and D(reals) (:101-102) as ONE pass: the two minibatches are interleaved so that
